@@ -6,7 +6,12 @@ batch of synthetic reads already in HBM (SURVEY.md section 8d stream: splitmix64
 150-bp reads, substitution rate 0.001, random strand).  Metric: k-mer instances per second
 (BASELINE.json: "Gkmer/s extracted+counted (k=47, 150 bp synthetic reads)").
 
-    python bench.py --gpus N --steps K --warmup W [--reads R] [--k 47]
+    python bench.py --gpus N --steps K --warmup W [--reads R] [--k 47] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (per-kernel HIP-event times of those steps
+included).  --full adds the secondary measurements: other shapes on the same reads, the CPU baseline, the host-memory
+boundary, the unitig compression of BASELINE config 3 and the slab write probe.  --dump-outputs DIR writes the table of the
+last timed step as .npy files (dump_table).
 
 N > 1 is launched by torch.distributed.run, one rank per GPU; see DESIGN.md (multi-GPU).
 """
@@ -97,6 +102,63 @@ def shape_kernel_rows(shape, k, kernel_ms, n_inst, n_recs, src_sha):
     return {"kernels": rows, "traffic_source": os.path.basename(tf[-1]) if tf else None, "traffic_stale": stale if tf else None}
 
 
+DUMP_SAMPLE_ROWS = 1 << 19          # rows of the table written by --dump-outputs (all of them if there are fewer)
+DUMP_MAX_SET_VALS = 1 << 21         # label-list values of those rows, at most
+DUMP_SEED = 0xDB6D
+
+
+def dump_table(tab, dev, out_dir, suffix, digest=None):
+    """--dump-outputs: the device-resident table one step returned (_capi.KmerTable) -> out_dir/<name><suffix>.npy, ~40 MB at
+    the most.  table_size: [valid k-mers, k-mer instances]; table_digest: the order-independent digest of every row
+    (distributed.table_digest) as two 32-bit halves; sample_rows: positions of a fixed, seeded sample of rows (the table is in
+    ascending key order), and for those rows the key words as exact 32-bit halves, exts, count, the length of each label list
+    and the lists' values one after another.  u64 words are split so that float64 holds them exactly."""
+    import numpy as np
+    import torch
+    D = importlib.import_module("rust-debruijn_amd.distributed")
+    os.makedirs(out_dir, exist_ok=True)
+    n = int(tab.n)
+    if digest is None:
+        digest = D.table_digest(tab, dev)
+    if n <= DUMP_SAMPLE_ROWS:
+        pos = np.arange(n, dtype=np.int64)
+    else:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE_ROWS, replace=False)).astype(np.int64)
+    it = torch.from_numpy(pos).to(dev)
+    masks = {"<i8": None, "<i4": 0xFFFFFFFF, "<i2": 0xFFFF, "|u1": None}
+
+    def col(ptr, count, typestr, index):
+        if not ptr or count == 0:
+            return np.zeros(len(index), np.uint64)
+        v = D._dev_tensor(ptr, count, typestr, dev)[index].to(torch.int64)
+        if masks[typestr] is not None:
+            v = v & masks[typestr]
+        return v.cpu().numpy().view(np.uint64)
+
+    out = {"table_size": np.array([n, int(tab.n_kmer_instances)], np.float64),
+           "table_digest": np.array([digest & 0xFFFFFFFF, digest >> 32], np.float64),
+           "sample_rows": pos.astype(np.float64)}
+    for nm, ptr in (("key_hi", tab.key_hi), ("key_lo", tab.key_lo)):
+        w = col(ptr, n, "<i8", it)
+        out[nm + "_lo32"] = (w & np.uint64(0xFFFFFFFF)).astype(np.float64)
+        out[nm + "_hi32"] = (w >> np.uint64(32)).astype(np.float64)
+    out["exts"] = col(tab.exts, n, "|u1", it).astype(np.float32)
+    if tab.count:
+        out["count"] = col(tab.count, n, "<i2", it).astype(np.float32)
+    if tab.set_off and n:
+        off_t = "<i4" if tab.set_off_width == 4 else "<i8"
+        val_t = {1: "|u1", 2: "<i2"}.get(int(tab.set_val_width), "<i4")
+        a = col(tab.set_off, n + 1, off_t, it).astype(np.int64)
+        b = col(tab.set_off, n + 1, off_t, it + 1).astype(np.int64)
+        lens = b - a
+        out["set_len"] = lens.astype(np.float32)
+        vi = np.repeat(a - np.concatenate(([0], np.cumsum(lens)[:-1])), lens) + np.arange(int(lens.sum()), dtype=np.int64)
+        vi = vi[:DUMP_MAX_SET_VALS]
+        out["set_val"] = col(tab.set_val, int(tab.n_set_val), val_t, torch.from_numpy(vi).to(dev)).astype(np.float64)
+    for nm, arr in out.items():
+        np.save(os.path.join(out_dir, nm + suffix + ".npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -132,7 +194,15 @@ def main():
     ap.add_argument("--no-other-shapes", action="store_true", help="skip the secondary shapes (k = 31, 63, 24; CountFilter) timed on the same reads")
     ap.add_argument("--compress-reads", type=int, default=-1,
                     help="reads of the stream used for the secondary unitigs/s measurement (0 = skip, -1 = all: BASELINE config 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements after the timed steps (other shapes, CPU baseline, host boundary, "
+                         "compress, slab write probe; each --no-* option above still skips its part)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the table of the last timed step to DIR/<name>.npy (float32 / float64; row count, digest of every "
+                         "row and a fixed seeded sample of rows; one set per rank, suffix _rank<r>, when N > 1)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started by hand as `python bench.py --gpus N`: become the launcher the driver would have used, one rank per GPU
@@ -209,13 +279,18 @@ def main():
     engine = D.HipEngine(ctx, dev)
     xstats = {}
 
-    def step():
+    kept = []                                           # the last step's table when --dump-outputs asks for it (freed after the dump)
+
+    def step(keep=False):
         if world == 1 and not args.force_sharded:
             # the drop-in entry point: filter_kmers, device-resident in and out
             t = capi.KmerTable()
             ctx.check(lib.dbg_filter_kmers_dev(ctx.h, C.byref(ss), C.byref(fp), C.byref(t)))
             res = (t.n, t.n_kmer_instances, D.table_digest(t, dev) if args.digest else 0)
-            lib.dbg_free_table(ctx.h, C.byref(t))
+            if keep:
+                kept.append(t)
+            else:
+                lib.dbg_free_table(ctx.h, C.byref(t))
             return res
         # N > 1: scan local reads -> all-to-all of minimizer-bin slabs (RCCL over xGMI) -> count owned bins
         st = {}
@@ -230,7 +305,10 @@ def main():
             else:
                 xstats[kk] = xstats.get(kk, 0) + v
         res = (tab.n, n_local, D.table_digest(tab, dev) if args.digest else 0)
-        engine.free_table(tab)
+        if keep:
+            kept.append(tab)
+        else:
+            engine.free_table(tab)
         return res
 
     def barrier():
@@ -248,8 +326,8 @@ def main():
     n_valid = n_inst = digest = 0
     ktimes = {}
     kseries = {}                                        # per-step HIP-event ms of each kernel: a bimodal scan shows here, not in a mean
-    for _ in range(args.steps):
-        n_valid, n_inst, digest = step()
+    for i in range(args.steps):
+        n_valid, n_inst, digest = step(keep=bool(args.dump_outputs) and i == args.steps - 1)
         for kt in ctx.timings():
             a = ktimes.setdefault(kt["name"], dict(ms=0.0, launches=0, units=0))
             a["ms"] += kt["ms"]; a["launches"] += kt["launches"]; a["units"] += kt["units"]
@@ -257,6 +335,9 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     ctx.enable_timing(False)
+    if kept:
+        dump_table(kept[0], dev, args.dump_outputs, "_rank%d" % rank if world > 1 else "", digest if args.digest else None)
+        lib.dbg_free_table(ctx.h, C.byref(kept.pop()))
     if world > 1:
         import torch.distributed as dist
         rdev = dev if args.backend == "nccl" else torch.device("cpu")
@@ -303,7 +384,7 @@ def main():
     slab = None
     try:
         cst = ctx.stats()
-        pr = ctx.probe_slab()
+        pr = ctx.probe_slab() if args.full else None        # (a measurement of its own: --full)
         slab = {"backing": cst["slab_backing_name"], "gb": round(cst["slab_bytes"] / 2**30, 2), "note": cst["slab_note"] or None,
                 # slab tournament: first-scan ms of the candidate blocks the first calls tried; the fastest one stayed (it needs DBG_SLAB_TRIALS = 4
                 # calls: --warmup >= 4 keeps the trials out of the timed steps)
@@ -429,7 +510,7 @@ def main():
                     "kernel_ms_min_med_max": {n: [min(v), sorted(v)[len(v) // 2], max(v)] for n, v in kseries.items() if n != "sk_records" and v},
                     "kernel_ms_by_step": {n: v for n, v in kseries.items() if n in ("sk_scan", "bin_count")}}
         other = None
-        if world == 1 and not args.force_sharded and not args.no_other_shapes:
+        if args.full and world == 1 and not args.force_sharded and not args.no_other_shapes:
             # the shapes the crate is used with day to day, on the same reads (BASELINE configs 4 / 5 per-GPU k, Kmer32's neighbourhood,
             # the plain counter): two timed steps each after one warm-up, per-kernel ms included
             other = {}
@@ -472,7 +553,7 @@ def main():
             del lab5k
             ctx.trim()                                               # (one tournament winner per shape sits in the pool)
         cpu = None
-        if not args.no_cpu_baseline and world == 1:                # timed on rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # timed on rank 0 at N = 1 only
             import oracle_lib as O
             n_s = 500000                                       # ~52M k-mer instances: ~8 s of single-thread CPU work (the rate does not depend on the sample size)
             hs = dbg.synth_reads_host(n_reads=n_s, read_len=L, genome_len=n_s * L // 30, error_rate=args.error_rate,
@@ -516,7 +597,7 @@ def main():
                                               "msp_sequence(p=8) -> %d shards -> filter_kmers per shard on %d threads, %.1f s"
                                               % (n_m, n_m * (L - k + 1) / 1e6, 16 * nt, nt, msec)}
         hostb = None
-        if not args.no_host_boundary and world == 1:
+        if args.full and not args.no_host_boundary and world == 1:
             # The reference's own boundary (filter.rs:139-148): the caller's reads in (pageable) host memory, the table back in
             # host memory.  PCIe-inclusive, so it is never `value`; CountFilter is the north-star figure, CountFilterSet = the
             # bench workload.  First call of each kind warms the ctx's pinned result pool (hipHostMalloc is slow), second is timed.
@@ -547,7 +628,7 @@ def main():
             hostb["pcie_bound_note"] = "(GB in + GB out) / 57 GB/s + ~0.08 s of kernels that no copy can hide"
             del hw, hst, hl, hc
         comp = None
-        if args.compress_reads and world == 1:
+        if args.full and args.compress_reads and world == 1:
             # second half of the metric ("+ unitigs/s compressed"): CountFilter(2) table of a prefix of the same
             # stream -> host (the Rust caller holds a BoomHashMap2 in host memory) -> compress_kmers_with_hash.
             # Timed end to end at the host boundary: H2D of the index, device links + unitig construction, D2H.

@@ -5,7 +5,7 @@ export PYTHONUNBUFFERED=1
 timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | tail -6 > gpurun_out/${R}_gputest_tail.txt; cat gpurun_out/${R}_gputest_tail.txt
 bash tools/pmc_round.sh $R > gpurun_out/${R}_pmc_round.log 2>&1; tail -3 gpurun_out/${R}_pmc_round.log
 cp gpurun_out/${R}_pmc_traffic_60Mreads.json profiles/${R}_pmc_traffic_60Mreads.json      # (on the box: the default bench reads the newest traffic file under profiles/)
-timeout 900 python bench.py > gpurun_out/${R}_bench_default.json 2> gpurun_out/${R}_bench_default.err; tail -c 1500 gpurun_out/${R}_bench_default.json | head -c 1400; echo
+B=${BENCH_OUT:-${TMPDIR:-/tmp}}; timeout 900 python bench.py --full > $B/${R}_bench_default.json 2> $B/${R}_bench_default.err; tail -c 1500 $B/${R}_bench_default.json | head -c 1400; echo
 bash tools/k_sweep.sh $R > gpurun_out/${R}_k_sweep.log 2>&1; tail -13 gpurun_out/${R}_k_sweep.log | cut -c1-200
 bash tools/other_configs.sh $R > gpurun_out/${R}_other_configs.log 2>&1; tail -7 gpurun_out/${R}_other_configs.log | cut -c1-260
 rm -f gpurun_out/${R}_second_stage.txt

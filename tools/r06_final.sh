@@ -9,9 +9,9 @@ bash tools/r06_pmc_shapes.sh $R > gpurun_out/${R}_pmc_shapes.log 2>&1; tail -6 g
 cp gpurun_out/${R}_pmc_shape_*.json profiles/ 2>/dev/null
 # the driver's command, three fresh processes
 for i in 1 2 3; do
-  timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/${R}_bench_default_$i.json 2> gpurun_out/${R}_bench_default_$i.err
+  B=${BENCH_OUT:-${TMPDIR:-/tmp}}; timeout 900 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $B/${R}_bench_default_$i.json 2> $B/${R}_bench_default_$i.err
   python3 -c "
-import json; j=json.loads(open('gpurun_out/${R}_bench_default_$i.json').read().strip().splitlines()[-1]); r=j['roofline']
+import json; j=json.loads(open('$B/${R}_bench_default_$i.json').read().strip().splitlines()[-1]); r=j['roofline']
 print('bench $i', j['value'], j['ms_per_step'], r['kernel_ms_per_step'], 'scan', r['kernel_ms_min_med_max']['sk_scan'], j['slab']['tournament_scan_ms'], 'censored', j['compress']['censored']['warm']['seconds'], j['compress']['censored']['first_call_fresh_ctx']['seconds'])"
 done
 timeout 600 python3 bench.py --gpus 1 --reads 100000000 --steps 1 --warmup 0 --digest --no-cpu-baseline --no-host-boundary --compress-reads 0 --no-other-shapes 2>/dev/null | grep '^{' | python3 -c "

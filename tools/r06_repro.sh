@@ -3,7 +3,7 @@
 # usage: tools/r06_repro.sh [tag] [n]
 R=${1:-r06a}; N=${2:-4}
 export PYTHONUNBUFFERED=1
-Q="--no-cpu-baseline --no-host-boundary --compress-reads 0 --no-other-shapes"
+Q="--full --no-cpu-baseline --no-host-boundary --compress-reads 0 --no-other-shapes"      # (--full: the slab write probe)
 for i in $(seq 1 $N); do
   timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 $Q > gpurun_out/${R}_s20_$i.json 2> gpurun_out/${R}_s20_$i.err
 done

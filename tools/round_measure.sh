@@ -4,7 +4,7 @@ R=${1:-r03}
 export PYTHONUNBUFFERED=1
 mkdir -p gpurun_out
 timeout 1500 python -m pytest tests -m gpu -q -x --durations=15 > gpurun_out/${R}_gputest.log 2>&1; tail -3 gpurun_out/${R}_gputest.log
-timeout 600 python bench.py --steps 20 --warmup 5 > gpurun_out/${R}_bench_default.json 2> gpurun_out/${R}_bench_default.err; tail -c 600 gpurun_out/${R}_bench_default.json
+B=${BENCH_OUT:-${TMPDIR:-/tmp}}; timeout 600 python bench.py --full --steps 20 --warmup 5 > $B/${R}_bench_default.json 2> $B/${R}_bench_default.err; tail -c 600 $B/${R}_bench_default.json
 timeout 400 bash tools/prof.sh $R --no-host-boundary > gpurun_out/prof_$R.log 2>&1; tail -3 gpurun_out/prof_$R.log
 timeout 900 bash tools/other_configs.sh $R > gpurun_out/${R}_other_configs.log 2>&1; tail -2 gpurun_out/${R}_other_configs.log
 timeout 600 python tools/bench_colours.py 4 24 40 64 100 250 > gpurun_out/${R}_colours.txt 2>&1; tail -4 gpurun_out/${R}_colours.txt
