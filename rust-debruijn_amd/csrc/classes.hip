@@ -170,15 +170,20 @@ extern "C" int dbg_label_classes_dev(dbg_ctx* c, uint64_t n, const uint64_t* set
 // label list (CountFilterSet)
 extern "C" int dbg_compress_table_dev(dbg_ctx* c, uint32_t k, int stranded, int spec, const dbg_kmer_table* t, dbg_graph* out,
                                       dbg_label_classes* classes) {
+    return compress_table_dev(c, k, stranded, spec, t, out, classes, nullptr);
+}
+
+int compress_table_dev(dbg_ctx* c, uint32_t k, int stranded, int spec, const dbg_kmer_table* t, dbg_graph* out, dbg_label_classes* classes,
+                       GraphDev* dev_out) {
     if (!t || !out) return c->fail(10, "null argument");
     if (!t->on_device) return c->fail(162, "dbg_compress_table_dev needs a device-resident table");
     if (classes) memset(classes, 0, sizeof(*classes));
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!t->set_off) return dbg_compress_kmers_with_hash_dev(c, k, stranded, spec, t->n, t->key_hi, t->key_lo, t->exts, nullptr, t->count, out);
+    if (!t->set_off) return compress_kmers_dev(c, k, stranded, spec, t->n, t->key_hi, t->key_lo, t->exts, nullptr, t->count, out, dev_out);
     DBuf<uint32_t> cls;
     ALLOC_OR_FAIL(c, cls, std::max<uint64_t>(t->n, 1));
     DBG_TRY(label_classes_device(c, t->n, t->set_off, t->set_val, t->n_set_val, cls.p, classes));
-    const int r = dbg_compress_kmers_with_hash_dev(c, k, stranded, spec, t->n, t->key_hi, t->key_lo, t->exts, cls.p, nullptr, out);
+    const int r = compress_kmers_dev(c, k, stranded, spec, t->n, t->key_hi, t->key_lo, t->exts, cls.p, nullptr, out, dev_out);
     if (r && classes) dbg_free_label_classes(classes);
     return r;
 }

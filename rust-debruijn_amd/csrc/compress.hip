@@ -268,11 +268,6 @@ struct BitPusher {          // DnaString::push (dna_string.rs:303-310) into a gr
 };
 }  // namespace
 
-struct UnitigNodes;
-int compress_links_device(dbg_ctx* c, int k, uint32_t n, const uint64_t* key_hi, const uint64_t* key_lo, const uint8_t* exts,
-                          const uint32_t* data, uint32_t* link_dev, const uint32_t* rank_dev, int spec, int stranded,
-                          dbg_graph* out, bool* done, const UnitigNodes* nodes = nullptr, const NodeRec* nrec = nullptr);
-
 // packed {key, Exts} records for the link builder's probes (k <= 60); *t gets them attached
 static int attach_key_records(dbg_ctx* c, KeysDev* t, int k, const uint8_t* exts_dev, DBuf<ulonglong2>* store, uint32_t* sorted_flag = nullptr) {
     if (k > 60 || !t->n || c->opt("DBG_NO_KEY_RECORDS")) return 0;
@@ -394,8 +389,8 @@ extern "C" int dbg_compress_kmers_with_hash(dbg_ctx* c, uint32_t k_, int strande
                 HIP_TRY(c, hipMemcpyAsync(d_rank.p, rank_h.data(), n * 4, hipMemcpyHostToDevice, c->stream));
             }
             bool done = false;
-            DBG_TRY(compress_links_device(c, k, (uint32_t)n, has_hi ? d_hi.p : nullptr, d_lo.p, d_exts.p, d_data.p, d_link.p,
-                                          rank_h.empty() ? nullptr : d_rank.p, spec, stranded, out, &done, nullptr, d_nrec.p));
+            DBG_TRY(compress_links_device(c, {k, (uint32_t)n, has_hi ? d_hi.p : nullptr, d_lo.p, d_exts.p, d_data.p, d_link.p,
+                                              rank_h.empty() ? nullptr : d_rank.p, spec, stranded, nullptr, d_nrec.p}, out, nullptr, &done));
             if (done) return 0;
             if (mode && !strcmp(mode, "device")) return c->fail(48, "DBG_COMPRESS=device but the neighbour links are not mutual");
             // links were only modified if cycles were cut, which happens after the mutuality check passed
@@ -479,9 +474,14 @@ extern "C" int dbg_compress_kmers_with_hash(dbg_ctx* c, uint32_t k_, int strande
 
 // Device-resident index in (the table dbg_filter_kmers_dev returns: ascending keys), host BaseGraph out.  Seed order =
 // ascending key (policy B).  data: data_dev (u32) if given, else count16_dev widened, else zeros.
-extern "C" int dbg_compress_kmers_with_hash_dev(dbg_ctx* c, uint32_t k_, int stranded, int spec, uint64_t n,
+extern "C" int dbg_compress_kmers_with_hash_dev(dbg_ctx* c, uint32_t k, int stranded, int spec, uint64_t n,
                                                 const uint64_t* key_hi_dev, const uint64_t* key_lo_dev, const uint8_t* exts_dev,
                                                 const uint32_t* data_dev, const uint16_t* count16_dev, dbg_graph* out) {
+    return compress_kmers_dev(c, k, stranded, spec, n, key_hi_dev, key_lo_dev, exts_dev, data_dev, count16_dev, out, nullptr);
+}
+
+int compress_kmers_dev(dbg_ctx* c, uint32_t k_, int stranded, int spec, uint64_t n, const uint64_t* key_hi_dev, const uint64_t* key_lo_dev,
+                       const uint8_t* exts_dev, const uint32_t* data_dev, const uint16_t* count16_dev, dbg_graph* out, GraphDev* dev_out) {
     const int k = (int)k_;
     if (k < 1 || k > 64) return c->fail(40, "k must be in 1..=64");
     if (spec < 0 || spec > 4) return c->fail(41, "unknown CompressionSpec");
@@ -526,7 +526,8 @@ extern "C" int dbg_compress_kmers_with_hash_dev(dbg_ctx* c, uint32_t k_, int str
     if (lr) return lr;
     d_rec.release();
     bool done = false;
-    DBG_TRY(compress_links_device(c, k, (uint32_t)n, t.hi, t.lo, exts_dev, d_data, d_link.p, nullptr, spec, stranded, out, &done, nullptr, d_nrec.p));
+    DBG_TRY(compress_links_device(c, {k, (uint32_t)n, t.hi, t.lo, exts_dev, d_data, d_link.p, nullptr, spec, stranded, nullptr, d_nrec.p},
+                                  dev_out ? nullptr : out, dev_out, &done));
     if (done) return 0;
     // inconsistent Exts (non-mutual links): the literal walk needs the index on the host
     std::vector<uint64_t> h_hi(has_hi ? n : 0), h_lo(n); std::vector<uint8_t> h_ex(n); std::vector<uint32_t> h_da(d_data ? n : 0);

@@ -138,6 +138,24 @@ struct __attribute__((aligned(32))) NodeRec {
     uint32_t exts;
 };
 
+// What one unitig construction reads.  link[side * n + i]: the elements' mutual links, cut where cycles are cut (in nrec too,
+// when the k-mers have records).  rank: seed rank of every element, null for the identity.  nodes: graph nodes as the elements
+// (compress_graph), null for k-mers (key_hi null when k <= 32).
+struct UnitigCall {
+    int k;
+    uint32_t n;
+    const uint64_t *key_hi, *key_lo;
+    const uint8_t* exts;
+    const uint32_t* data;
+    uint32_t* link;
+    const uint32_t* rank;
+    int spec, stranded;
+    const UnitigNodes* nodes;
+    NodeRec* nrec;
+};
+// device counters of the segment route's second level: the seed element of every cycle cut_cycles_kernel cuts (at most cap)
+struct CycleSeeds { uint32_t* list; uint32_t* count; uint32_t cap; };
+
 // A BaseGraph (graph.rs:43-50) resident in HBM: what the rank-spanning second stage passes from step to step and sends
 // between ranks (graph.hip).  words carries at least two zero words of slack behind n_words (k-mer fetches need no clamp).
 struct GraphDev {
@@ -150,7 +168,15 @@ struct GraphDev {
     bool filled = false;
 };
 
-int graph_dev_join_segments(struct dbg_ctx* c, int k, int stranded, int spec, GraphDev* in, GraphDev* out);   // graph.hip
+// the BaseGraph of one construction goes to exactly one of out (host) and dev_out (HBM)
+int compress_links_device(dbg_ctx* c, const UnitigCall& u, dbg_graph* out, GraphDev* dev_out, bool* done, const CycleSeeds* seeds = nullptr);
+int graph_dev_join_segments(dbg_ctx* c, int k, int stranded, int spec, GraphDev* in, GraphDev* out, const CycleSeeds* seeds);   // graph.hip
+// compress_kmers_with_hash on a device-resident index (compress.hip) / table (classes.hip); dev_out: the graph stays in HBM there
+// when the device route takes the call (dev_out->filled), otherwise the literal walk leaves it in *out
+int compress_kmers_dev(dbg_ctx* c, uint32_t k, int stranded, int spec, uint64_t n, const uint64_t* key_hi_dev, const uint64_t* key_lo_dev,
+                       const uint8_t* exts_dev, const uint32_t* data_dev, const uint16_t* count16_dev, dbg_graph* out, GraphDev* dev_out);
+int compress_table_dev(dbg_ctx* c, uint32_t k, int stranded, int spec, const dbg_kmer_table* t, dbg_graph* out, dbg_label_classes* classes,
+                       GraphDev* dev_out);
 
 // ---- launch helpers -----------------------------------------------------------------------
 #define LAUNCH_CHECK(ctx, name)                                                                 \

@@ -14,10 +14,6 @@
 #include <deque>
 #include <cstring>
 
-int compress_links_device(dbg_ctx* c, int k, uint32_t n, const uint64_t* key_hi, const uint64_t* key_lo, const uint8_t* exts,
-                          const uint32_t* data, uint32_t* link_dev, const uint32_t* rank_dev, int spec, int stranded,
-                          dbg_graph* out, bool* done, const UnitigNodes* nodes, const NodeRec* nrec = nullptr);
-
 namespace {
 
 struct EndIndex {            // sorted terminal k-mers of one side + owning node
@@ -411,7 +407,7 @@ extern "C" int dbg_compress_graph(dbg_ctx* c, uint32_t k_, int stranded, int spe
             UnitigNodes un{u_weight.p, d.words.p, d.start.p, d.length.p, n_censor ? d_avail.p : nullptr};
             dbg_graph ng;
             bool done = false;
-            DBG_TRY(compress_links_device(c, k, n, nullptr, nullptr, d.exts.p, d.data.p, u_link.p, nullptr, spec, stranded, &ng, &done, &un));
+            DBG_TRY(compress_links_device(c, {k, n, nullptr, nullptr, d.exts.p, d.data.p, u_link.p, nullptr, spec, stranded, &un, nullptr}, &ng, nullptr, &done));
             if (done) {
                 // ---- graph.finish(); dbg.fix_exts(None) (compression.rs:330-331) ----
                 DevGraph d2;
@@ -622,11 +618,9 @@ extern "C" int dbg_graph_write_gfa(dbg_ctx* c, uint32_t k, const dbg_graph* g, c
 // Reference flow: per-shard compress_kmers_with_hash -> BaseGraph::combine (graph.rs:71-100) -> compress_graph
 // (compression.rs:291-349), src/test.rs:459-470.  Rounds 2-3 ran it in Python: every rank's graph device -> host numpy ->
 // device -> p2p -> host, and one rank combined on the host.  Here a shard graph never leaves HBM between the steps: the unitig
-// construction hands its buffers over (dbg_ctx::graph_sink), combine is a packing kernel, compress_graph runs its device
+// construction hands its buffers over (compress_table_dev into a GraphDev), combine is a packing kernel, compress_graph runs its device
 // route on device-resident nodes, and graphs travel as device buffers over the dbg_transport.
 // ================================================================================================
-extern "C" int dbg_compress_table_dev(dbg_ctx* c, uint32_t k, int stranded, int spec, const dbg_kmer_table* t, dbg_graph* out,
-                                      dbg_label_classes* classes);
 #include "shard_comm.hpp"
 namespace {
 
@@ -765,7 +759,8 @@ __global__ void __launch_bounds__(256) short_node_kernel(const uint32_t* __restr
 // partial (an inner level of the tree merge): the graph holds SOME of the shards, so an extension whose k-mer is in no node
 // points into a shard that has not arrived yet: such a path ends there for now, and neither fix_exts runs -- stripping the Exts
 // that have no target yet (compression.rs:309, :331) would cut the graph at the shard boundary for good.
-int graph_dev_compress(dbg_ctx* c, int k, int stranded, int spec, GraphDev* in, GraphDev* out, bool partial = false) {
+// seeds: the cycles the unitig construction cuts at their seeds are reported there (the segment route's second level).
+int graph_dev_compress(dbg_ctx* c, int k, int stranded, int spec, GraphDev* in, GraphDev* out, bool partial = false, const CycleSeeds* seeds = nullptr) {
     const uint64_t n64 = in->n_nodes;
     if (n64 >= (1ull << 30)) return c->fail(51, "compress_graph: at most 2^30-1 nodes per call in this build");
     const uint32_t n = (uint32_t)n64;
@@ -801,11 +796,7 @@ int graph_dev_compress(dbg_ctx* c, int k, int stranded, int spec, GraphDev* in, 
         node_links_to_unitig_kernel<<<cdiv(2 * (uint64_t)n, 256), 256, 0, c->stream>>>(d_link.p, d.length.p, n, k, u_link.p, u_weight.p);
         LAUNCH_CHECK(c, "node_links_to_unitig");
         UnitigNodes un{u_weight.p, d.words.p, d.start.p, d.length.p, nullptr};
-        dbg_graph ng;
-        c->graph_sink = &sink;
-        const int r = compress_links_device(c, k, n, nullptr, nullptr, d.exts.p, d.data.p, u_link.p, nullptr, spec, stranded, &ng, &done, &un);
-        c->graph_sink = nullptr;
-        if (r) return r;
+        DBG_TRY(compress_links_device(c, {k, n, nullptr, nullptr, d.exts.p, d.data.p, u_link.p, nullptr, spec, stranded, &un, nullptr}, nullptr, &sink, &done, seeds));
         if (!done && partial)
             return c->fail(48, "tree reduce: the node links of a partial merge are not mutual (inconsistent Exts: input on which the reference's compress_graph "
                                "panics or depends on visiting order); DBG_REDUCE_GATHER takes the literal walk for such input");
@@ -954,8 +945,8 @@ int gather_blobs(dbg_ctx* c, ShardComm& X, int lrc, const std::vector<uint8_t>& 
 
 // compress_graph's device route on a device-resident graph without either fix_exts: the second level of unitig.hip's segment route
 // (segments of long chains -> unitigs; a segment end whose extension leads into no node end is a chain end, as at the k-mer level)
-int graph_dev_join_segments(dbg_ctx* c, int k, int stranded, int spec, GraphDev* in, GraphDev* out) {
-    return graph_dev_compress(c, k, stranded, spec, in, out, true);
+int graph_dev_join_segments(dbg_ctx* c, int k, int stranded, int spec, GraphDev* in, GraphDev* out, const CycleSeeds* seeds) {
+    return graph_dev_compress(c, k, stranded, spec, in, out, true, seeds);
 }
 
 extern "C" int dbg_shard_compress_dev(dbg_ctx* c, const dbg_transport* tr, uint32_t k, int stranded, int spec, int second_spec,
@@ -1004,10 +995,7 @@ extern "C" int dbg_shard_compress_dev(dbg_ctx* c, const dbg_transport* tr, uint3
         if (X.inject("shard")) return X.injected("shard");
         dbg_graph hg;
         memset(&hg, 0, sizeof(hg));
-        c->graph_sink = &mine;
-        const int r = dbg_compress_table_dev(c, k, stranded, spec, table, &hg, table->set_off ? &lc : nullptr);
-        c->graph_sink = nullptr;
-        if (r) return r;
+        DBG_TRY(compress_table_dev(c, k, stranded, spec, table, &hg, table->set_off ? &lc : nullptr, &mine));
         if (!mine.filled) {                     // the literal host walk ran (or the table is empty): the result is on the host
             if (hg.n_nodes) { const int r2 = graph_dev_from_host(c, &hg, &mine); if (r2) { dbg_free_graph(c, &hg); return r2; } }
             else { GraphDev e; if (int r3 = graph_dev_from_host(c, &hg, &e)) return r3; mine = std::move(e); }

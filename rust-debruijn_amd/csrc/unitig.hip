@@ -8,14 +8,17 @@
 //   * a chain becomes one node; its seed is the member with the smallest seed rank; the node's sequence is
 //     read in the seed's stored orientation; nodes are emitted in increasing seed rank;
 //   * an isolated cycle is cut at the right side of its seed (the left walk consumes the whole cycle first).
-// That makes the construction data-parallel.  Three routes, fastest first (compress_links_device picks):
+// That makes the construction data-parallel.  Four routes, fastest first (compress_links_device picks):
 //   1. chain route (k-mer tables): every chain end walks its chain (chain_scan_kernel: length, seed, which end is the
 //      unitig's left end); after two prefix sums one lane per node walks it again and writes it front to back
 //      (chain_emit_kernel).  No per-state table; one cache line per step when link_kernel left NodeRec records.
-//   2. end walk into a table (compress_graph, or route 1 switched off): walk_ends_kernel leaves in every state "(element,
+//   2. segment route (k-mer tables whose chains are long or beyond the chain route's cap): every 128th k-mer cuts its right
+//      link in a copy of the links, the pieces take the chain route, compress_graph's device route joins them
+//      (graph_dev_join_segments); cycles are cut at their seeds and the route runs again, at most three times.
+//   3. end walk into a table (compress_graph, or route 1 switched off): walk_ends_kernel leaves in every state "(element,
 //      side I leave through)" its distance to the chain end it faces, that end and the minimum rank on the way; then
 //      per-element arithmetic, two prefix sums and atomic ORs into the packed output (emit_kernel / emit_nodes_kernel).
-//   3. doubling (jump_kernel): the same table by pointer jumping -- for cycles (cut at their seed, then redone) and for
+//   4. doubling (jump_kernel): the same table by pointer jumping -- for cycles (cut at their seed, then redone) and for
 //      chains too long to walk (WALK_CAP).
 // If the links are not mutual (inconsistent Exts, which also makes the reference panic or depend on visiting order)
 // the caller falls back to the literal host walk.
@@ -745,288 +748,292 @@ __global__ void cut_at_piece_seeds_kernel(const uint32_t* __restrict__ seed_piec
     atomicAdd(n_cut, 1u);
 }
 
-}  // namespace
+struct Chains {                         // what the chain route's first walk found; the per-rank arrays feed its emit
+    DBuf<uint32_t> flag_by_rank, len_by_rank, uidx_by_rank, start_by_rank, seed_by_rank, done_bits;
+    uint32_t n_ends = 0, cap = WALK_CAP;
+    bool long_chains = false, gave_up = false, ok = false;
+    uint64_t seen = 0;
+};
+// host arrays the chain route fills while its kernels run: start and length (`nodes`), the first `words` sequence words
+struct EarlyCopy { dbg_graph host{}; bool nodes = false; uint64_t words = 0; };
 
-// Builds the BaseGraph on the device from the neighbour links.  rank_dev: seed rank of every (sorted) k-mer id,
-// or null for the identity.  link_dev is modified when cycles are cut.  *done = false (nothing produced)
-// when the links are not mutual or contain a panic marker: the caller then runs the literal host walk.
-int compress_links_device(dbg_ctx* c, int k, uint32_t n, const uint64_t* key_hi, const uint64_t* key_lo, const uint8_t* exts,
-                          const uint32_t* data, uint32_t* link_dev, const uint32_t* rank_dev, int spec, int stranded,
-                          dbg_graph* out, bool* done, const UnitigNodes* nodes, const NodeRec* nrec) {
-    *done = false;
-    const uint32_t* weight = nodes ? nodes->weight : nullptr;
-    const uint8_t* avail = nodes ? nodes->avail : nullptr;
-    if (n == 0 || n >= (1u << 30)) return 0;
-    const uint32_t n2 = 2 * n;
-    DBuf<uint32_t> flags;
+// One construction: the call, the flags of its links' check and the scratch its routes share.  The segment route runs the chain
+// route on its pieces as a construction of its own.
+struct Unitigs : UnitigCall {
+    dbg_ctx* c;
+    const uint32_t n2;
+    const uint32_t* weight;
+    const uint8_t* avail;
+    DBuf<uint32_t> flags, LA, counters;
+    bool links_checked = false;
+    Unitigs(dbg_ctx* c_, const UnitigCall& u)
+        : UnitigCall(u), c(c_), n2(2 * u.n), weight(u.nodes ? u.nodes->weight : nullptr), avail(u.nodes ? u.nodes->avail : nullptr) {}
+    int open(bool walks_check, bool* bad);
+    int check_links(bool* bad);
+    int links_bad(bool* bad);
+    int chain_scan(bool force_segments, Chains& s, bool* bad);
+    int chain_emit(Chains& s, GraphDev* g, EarlyCopy* early);
+    int chain_route(uint32_t* outer_link, GraphDev* g, uint32_t* new_cuts);
+    int segment_route(uint64_t n_ends, GraphDev* g, bool* bad);
+    int table_route(const CycleSeeds* seeds, GraphDev* g, bool* bad);
+    int deliver(GraphDev& g, const EarlyCopy& early, dbg_graph* out, GraphDev* dev_out);
+};
+
+// walks_check: the chain route with node records checks the links while it walks them; everything else checks them first
+int Unitigs::open(bool walks_check, bool* bad) {
     ALLOC_OR_FAIL(c, flags, 2);
     HIP_TRY(c, hipMemsetAsync(flags.p, 0, 8, c->stream));
-    const bool try_chains = !nodes && !c->opt("DBG_UNITIG_NO_CHAINS") && !c->opt("DBG_UNITIG_NO_WALK");
-    // the chain route with node records checks the links while it walks them; everything else checks them first
-    bool links_checked = false;
-    auto check_links = [&]() -> int {
-        c->t_begin("unitig_check_links", n);
-        check_links_kernel<<<cdiv(n2, 256), 256, 0, c->stream>>>(link_dev, avail, n, flags.p);
-        c->t_end();
-        LAUNCH_CHECK(c, "check_links");
-        links_checked = true;
-        return 0;
-    };
-    auto links_bad = [&](bool* bad) -> int {
-        uint32_t fl[2] = {0, 0};
-        HIP_TRY(c, hipMemcpyAsync(fl, flags.p, 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        *bad = fl[0] != 0;
-        return 0;
-    };
-    if (!(try_chains && nrec)) {
-        DBG_TRY(check_links());
-        bool bad = false;
-        DBG_TRY(links_bad(&bad));
-        if (bad) return 0;
+    if (!walks_check) {
+        DBG_TRY(check_links(bad));
+        if (*bad) return 0;
     }
-
-    if (nodes && c->cycle_seed_count) {                             // (second level of the segment route)
-        self_loop_seeds_kernel<<<cdiv(n, 256), 256, 0, c->stream>>>(link_dev, n, c->cycle_seed_list, c->cycle_seed_count, c->cycle_seed_cap);
-        LAUNCH_CHECK(c, "self_loop_seeds");
-    }
-
-    DBuf<uint32_t> LA, counters;
     ALLOC_OR_FAIL(c, LA, n2);
     ALLOC_OR_FAIL(c, counters, 8);
-    // results of either route
-    DBuf<uint32_t> flag_by_rank, len_by_rank, uidx_by_rank, ulen, uexts, o_data, useed;
-    DBuf<uint64_t> ustart, words;
-    DBuf<unsigned long long> uacc;
-    DBuf<uint8_t> o_exts;
-    uint32_t n_nodes = 0;
-    uint64_t total_bases = 0, n_words = 0;
-    bool emitted = false, early_nodes = false;
-    uint64_t early_words = 0;
-    dbg_graph out_early{};                                         // host arrays the chain route fills while its kernels run
+    return 0;
+}
 
-    // ---- chain route (k-mers only): two walks per chain, no per-state table ----
-    if (try_chains) {
-        DBuf<uint32_t> start_by_rank, seed_by_rank, ufirst;
-        ALLOC_OR_FAIL(c, flag_by_rank, n); ALLOC_OR_FAIL(c, len_by_rank, n); ALLOC_OR_FAIL(c, uidx_by_rank, (size_t)n + 1);
-        ALLOC_OR_FAIL(c, start_by_rank, n); ALLOC_OR_FAIL(c, seed_by_rank, n);
-        HIP_TRY(c, hipMemsetAsync(flag_by_rank.p, 0, (size_t)n * 4, c->stream));
-        HIP_TRY(c, hipMemsetAsync(counters.p, 0, 32, c->stream));
-        c->t_begin("unitig_chain_scan", n);
-        collect_ends_kernel<<<cdiv(n2, 1024 * ENDS_ITEMS), 1024, 0, c->stream>>>(link_dev, nullptr, n, LA.p, counters.p, links_checked ? nullptr : flags.p);
-        LAUNCH_CHECK(c, "collect_ends");
-        uint32_t n_ends = 0;
-        HIP_TRY(c, hipMemcpyAsync(&n_ends, counters.p, 4, hipMemcpyDeviceToHost, c->stream));
+int Unitigs::check_links(bool* bad) {
+    c->t_begin("unitig_check_links", n);
+    check_links_kernel<<<cdiv(n2, 256), 256, 0, c->stream>>>(link, avail, n, flags.p);
+    c->t_end();
+    LAUNCH_CHECK(c, "check_links");
+    links_checked = true;
+    return links_bad(bad);
+}
+
+int Unitigs::links_bad(bool* bad) {
+    uint32_t fl[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(fl, flags.p, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *bad = fl[0] != 0;
+    return 0;
+}
+
+// ---- chain route (k-mers only): two walks per chain, no per-state table ----
+// The first walk: every chain end walks its chain.  s.ok: every k-mer sits on an open chain and no walker gave up.
+int Unitigs::chain_scan(bool force_segments, Chains& s, bool* bad) {
+    ALLOC_OR_FAIL(c, s.flag_by_rank, n); ALLOC_OR_FAIL(c, s.len_by_rank, n); ALLOC_OR_FAIL(c, s.uidx_by_rank, (size_t)n + 1);
+    ALLOC_OR_FAIL(c, s.start_by_rank, n); ALLOC_OR_FAIL(c, s.seed_by_rank, n);
+    HIP_TRY(c, hipMemsetAsync(s.flag_by_rank.p, 0, (size_t)n * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(counters.p, 0, 32, c->stream));
+    c->t_begin("unitig_chain_scan", n);
+    collect_ends_kernel<<<cdiv(n2, 1024 * ENDS_ITEMS), 1024, 0, c->stream>>>(link, nullptr, n, LA.p, counters.p, links_checked ? nullptr : flags.p);
+    LAUNCH_CHECK(c, "collect_ends");
+    HIP_TRY(c, hipMemcpyAsync(&s.n_ends, counters.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    // long chains (a censored graph: thousands of k-mers per chain) are not for this route -- its two walks per chain are as long
+    // as the longest chain, and they give up at WALK_CAP: straight to the table routes
+    if (const char* e = c->opt("DBG_CHAIN_CAP")) s.cap = (uint32_t)std::max(16, atoi(e));     // measurement / tests
+    // (force_segments, DBG_SEGMENTS_FORCE in tests: every graph takes the segment route, whatever the length of its chains)
+    s.long_chains = (s.n_ends && (uint64_t)n2 / s.n_ends > 512u && !c->opt("DBG_CHAIN_CAP")) || (force_segments && s.n_ends);
+    const bool one_walk = !(c->opt("DBG_CHAIN_WALKS") && !strcmp(c->opt("DBG_CHAIN_WALKS"), "2"));
+    if (s.n_ends && one_walk) {
+        ALLOC_OR_FAIL(c, s.done_bits, (size_t)(n2 + 31) / 32 + 1);
+        HIP_TRY(c, hipMemsetAsync(s.done_bits.p, 0, ((size_t)(n2 + 31) / 32 + 1) * 4, c->stream));
+    }
+    if (s.n_ends && !s.long_chains) {
+        chain_scan_kernel<<<std::min<uint32_t>(cdiv(s.n_ends, 256), 2048), 256, 0, c->stream>>>(
+            link, rank, n, LA.p, s.n_ends, k, s.flag_by_rank.p, s.len_by_rank.p, s.start_by_rank.p, s.seed_by_rank.p,
+            counters.p + 4, (unsigned long long*)(counters.p + 2), counters.p + 1, links_checked ? nullptr : nrec, flags.p, s.done_bits.p, s.cap);
+        LAUNCH_CHECK(c, "chain_scan");
+    }
+    uint32_t res[4] = {0, 0, 0, 0};
+    HIP_TRY(c, hipMemcpyAsync(res, counters.p, 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->t_end();
+    s.seen = (uint64_t)res[2] | ((uint64_t)res[3] << 32);
+    s.gave_up = res[1] != 0;
+    if (!links_checked) {                                          // the walk checked the links of the chains it covered
+        DBG_TRY(links_bad(bad));
+        if (*bad) return 0;
+    }
+    s.ok = !s.long_chains && !s.gave_up && s.seen == n;
+    if (c->opt("DBG_DEBUG")) fprintf(stderr, "[unitig] %u chain ends, chains hold %llu of %u k-mers%s\n", s.n_ends, (unsigned long long)s.seen, n,
+                                     s.ok ? "" : " -> general route");
+    return 0;
+}
+
+// The second walk: after two prefix sums one lane per node walks its chain again and writes it front to back, into g (with the
+// seed k-mer of every node).  early (a host destination): results leave while kernels still run.
+int Unitigs::chain_emit(Chains& s, GraphDev* g, EarlyCopy* early) {
+    uint32_t n_nodes = 0;
+    uint64_t total_bases = 0;
+    DBG_TRY(scan_exclusive_u32(c, s.flag_by_rank.p, s.uidx_by_rank.p, n));
+    HIP_TRY(c, hipMemcpyAsync(&n_nodes, s.uidx_by_rank.p + n, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const uint32_t nn = std::max<uint32_t>(n_nodes, 1);
+    DBuf<uint32_t> ufirst, uexts;
+    DBuf<unsigned long long> uacc;
+    ALLOC_OR_FAIL(c, g->length, nn); ALLOC_OR_FAIL(c, ufirst, nn); ALLOC_OR_FAIL(c, g->seed, nn);
+    ALLOC_OR_FAIL(c, g->start, (size_t)n_nodes + 1);
+    ALLOC_OR_FAIL(c, uexts, nn); ALLOC_OR_FAIL(c, uacc, nn); ALLOC_OR_FAIL(c, g->exts, nn); ALLOC_OR_FAIL(c, g->data, nn);
+    gather_chains_kernel<<<cdiv(n, 256), 256, 0, c->stream>>>(s.flag_by_rank.p, s.uidx_by_rank.p, s.len_by_rank.p, s.start_by_rank.p, s.seed_by_rank.p, n,
+                                                              g->length.p, ufirst.p, g->seed.p);
+    LAUNCH_CHECK(c, "gather_chains");
+    DBG_TRY(scan_exclusive_u32_u64(c, g->length.p, g->start.p, n_nodes));
+    HIP_TRY(c, hipMemcpyAsync(&total_bases, g->start.p + n_nodes, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const uint64_t n_words = (total_bases + 31) / 32;
+    ALLOC_OR_FAIL(c, g->words, n_words + 3);
+    HIP_TRY(c, hipMemsetAsync(g->words.p, 0, (n_words + 3) * 8, c->stream));
+    HIP_TRY(c, hipMemsetAsync(counters.p + 6, 0, 4, c->stream));
+    // The nodes are emitted in two halves so that results can leave while kernels still run: offsets and lengths are
+    // final already, the first half of the sequence words is final when the second half starts.  (A copy into pageable
+    // host memory blocks the host thread, not the device: it is issued on a second stream after the kernels it overlaps.)
+    if (early) {
+        // (pinned blocks from the ctx's result pool: a copy into pageable memory runs at a third of the link's rate and
+        //  takes a page fault per 4 KB of a fresh array -- 680 MB of graph at config-3 size cost ~40 ms that way)
+        early->host.seq_words = (uint64_t*)ctx_halloc(c, std::max<uint64_t>(n_words, 1) * 8);
+        early->host.start = (uint64_t*)ctx_halloc(c, (size_t)nn * 8);
+        early->host.length = (uint32_t*)ctx_halloc(c, (size_t)nn * 4);
+    }
+    hipStream_t cs = early ? c->get_copy_stream() : nullptr;
+    c->t_begin("unitig_emit", n);
+    if (n_nodes) {
+        const uint32_t half = n_nodes / 2;
+        uint64_t first_half_bases = 0;
+        if (half) HIP_TRY(c, hipMemcpyAsync(&first_half_bases, g->start.p + half, 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemsetAsync(counters.p + 6, 0, 8, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        // long chains (a censored graph: thousands of k-mers per chain) are not for this route -- its two walks per chain are as long
-        // as the longest chain, and they give up at WALK_CAP: straight to the table routes
-        uint32_t chain_cap = WALK_CAP;
-        if (const char* e = c->opt("DBG_CHAIN_CAP")) chain_cap = (uint32_t)std::max(16, atoi(e));     // measurement / tests
-        // (DBG_SEGMENTS_FORCE, tests: every graph takes the segment route below, whatever the length of its chains)
-        const bool force_segments = c->opt("DBG_SEGMENTS_FORCE") && c->segment_depth == 0 && n_ends;
-        const bool long_chains = (n_ends && (uint64_t)n2 / n_ends > 512u && !c->opt("DBG_CHAIN_CAP")) || force_segments;
-        DBuf<uint32_t> done_bits;
-        const bool one_walk = !(c->opt("DBG_CHAIN_WALKS") && !strcmp(c->opt("DBG_CHAIN_WALKS"), "2"));
-        if (n_ends && one_walk) {
-            ALLOC_OR_FAIL(c, done_bits, (size_t)(n2 + 31) / 32 + 1);
-            HIP_TRY(c, hipMemsetAsync(done_bits.p, 0, ((size_t)(n2 + 31) / 32 + 1) * 4, c->stream));
+        hipEvent_t ev = c->get_event();
+        if (half) {
+            chain_emit_kernel<<<std::min<uint32_t>(cdiv(half, 256), 2048), 256, 0, c->stream>>>(
+                link, n, k, key_hi, key_lo, exts, data, spec, 0, half, ufirst.p, g->seed.p, g->start.p, g->words.p, uexts.p, uacc.p, counters.p + 6, nrec);
+            LAUNCH_CHECK(c, "chain_emit");
         }
-        if (n_ends && !long_chains) {
-            chain_scan_kernel<<<std::min<uint32_t>(cdiv(n_ends, 256), 2048), 256, 0, c->stream>>>(
-                link_dev, rank_dev, n, LA.p, n_ends, k, flag_by_rank.p, len_by_rank.p, start_by_rank.p, seed_by_rank.p,
-                counters.p + 4, (unsigned long long*)(counters.p + 2), counters.p + 1, links_checked ? nullptr : nrec, flags.p, done_bits.p, chain_cap);
-            LAUNCH_CHECK(c, "chain_scan");
-        }
-        uint32_t res[4] = {0, 0, 0, 0};
-        HIP_TRY(c, hipMemcpyAsync(res, counters.p, 16, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->t_end();
-        const uint64_t seen = (uint64_t)res[2] | ((uint64_t)res[3] << 32);
-        if (!links_checked) {                                      // the walk checked the links of the chains it covered
-            bool bad = false;
-            DBG_TRY(links_bad(&bad));
-            if (bad) return 0;
-        }
-        const bool ok = !long_chains && res[1] == 0 && seen == n;  // no walker gave up, every k-mer sits on an open chain
-        if (c->opt("DBG_DEBUG")) fprintf(stderr, "[unitig] %u chain ends, chains hold %llu of %u k-mers%s\n", n_ends, (unsigned long long)seen, n,
-                                         ok ? "" : " -> general route");
-        if (!ok && c->segment_depth > 0) {
-            // first level of the segment route: k-mers no walker passed = cycles without a cut.  Found by a marking walk, cut at their seeds
-            // in the caller's links; the caller runs the route again (or, if nothing could be cut, the table route).
-            c->segment_new_cuts = 0;
-            if (res[1] == 0 && n_ends && c->segment_outer_links) {
-                DBuf<uint32_t> visited, cc;
-                const size_t vw = ((size_t)n + 31) / 32;
-                ALLOC_OR_FAIL(c, visited, vw); ALLOC_OR_FAIL(c, cc, 2);
-                HIP_TRY(c, hipMemsetAsync(visited.p, 0, vw * 4, c->stream));
-                HIP_TRY(c, hipMemsetAsync(cc.p, 0, 8, c->stream));
-                HIP_TRY(c, hipMemsetAsync(counters.p + 1, 0, 20, c->stream));       // the walk's own counters: capped, k-mers seen, next end
-                c->t_begin("unitig_chain_scan", n);
-                chain_scan_kernel<<<std::min<uint32_t>(cdiv(n_ends, 256), 2048), 256, 0, c->stream>>>(
-                    link_dev, rank_dev, n, LA.p, n_ends, k, flag_by_rank.p, len_by_rank.p, start_by_rank.p, seed_by_rank.p,
-                    counters.p + 4, (unsigned long long*)(counters.p + 2), counters.p + 1, nullptr, flags.p, nullptr, chain_cap, visited.p);
-                unvisited_cycle_seeds_kernel<<<cdiv(n, 256), 256, 0, c->stream>>>(link_dev, rank_dev, n, visited.p, c->segment_outer_links, const_cast<NodeRec*>(nrec), cc.p, cc.p + 1);
-                c->t_end();
-                LAUNCH_CHECK(c, "unvisited_cycle_seeds");
-                uint32_t h[2] = {0, 0};
-                HIP_TRY(c, hipMemcpyAsync(h, cc.p, 8, hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(c, hipStreamSynchronize(c->stream));
-                if (!h[1]) c->segment_new_cuts = h[0];
-                if (c->opt("DBG_DEBUG")) fprintf(stderr, "[unitig] segment route: %llu k-mers on cycles without a cut, %u cycles cut at their seeds%s\n", (unsigned long long)(n - seen), h[0], h[1] ? " (a walk gave up)" : "");
+        HIP_TRY(c, hipEventRecord(ev, c->stream));
+        chain_emit_kernel<<<std::min<uint32_t>(cdiv(n_nodes - half, 256), 2048), 256, 0, c->stream>>>(
+            link, n, k, key_hi, key_lo, exts, data, spec, half, n_nodes - half, ufirst.p, g->seed.p, g->start.p, g->words.p, uexts.p, uacc.p, counters.p + 7, nrec);
+        LAUNCH_CHECK(c, "chain_emit");
+        finish_nodes_kernel<<<cdiv(n_nodes, 256), 256, 0, c->stream>>>(n_nodes, spec, k, g->length.p, uexts.p, uacc.p, nullptr, g->exts.p, g->data.p);
+        LAUNCH_CHECK(c, "finish_nodes");
+        if (cs) {
+            HIP_TRY(c, hipMemcpyAsync(early->host.start, g->start.p, (size_t)n_nodes * 8, hipMemcpyDeviceToHost, cs));
+            HIP_TRY(c, hipMemcpyAsync(early->host.length, g->length.p, (size_t)n_nodes * 4, hipMemcpyDeviceToHost, cs));
+            early->nodes = true;
+            // words wholly inside the first half: the word that holds the boundary base may still receive bits
+            early->words = first_half_bases / 32;
+            if (early->words) {
+                HIP_TRY(c, hipStreamWaitEvent(cs, ev, 0));
+                HIP_TRY(c, hipMemcpyAsync(early->host.seq_words, g->words.p, early->words * 8, hipMemcpyDeviceToHost, cs));
             }
+            HIP_TRY(c, hipStreamSynchronize(cs));
+        }
+        c->event_pool.push_back(ev);
+    }
+    c->t_end();
+    g->n_nodes = n_nodes; g->n_words = n_words; g->n_bases = total_bases; g->stranded = stranded ? 1 : 0; g->filled = true;
+    return 0;
+}
+
+// The chain route alone, on the links the segment route cut (its first level): g->filled, the pieces with the seed k-mer of each
+// (for cycles found one level up).  Otherwise k-mers no walker passed are cycles without a cut: a marking walk finds them, and they
+// are cut at their seeds in outer_link, the call's own links -- *new_cuts of them (0: the table route takes the call).
+int Unitigs::chain_route(uint32_t* outer_link, GraphDev* g, uint32_t* new_cuts) {
+    bool bad = false;
+    DBG_TRY(open(nrec != nullptr, &bad));
+    if (bad) return 0;
+    Chains s;
+    DBG_TRY(chain_scan(false, s, &bad));
+    if (bad) return 0;
+    if (s.ok) {
+        DBG_TRY(chain_emit(s, g, nullptr));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return 0;
+    }
+    if (s.gave_up || !s.n_ends) return 0;
+    DBuf<uint32_t> visited, cc;
+    const size_t vw = ((size_t)n + 31) / 32;
+    ALLOC_OR_FAIL(c, visited, vw); ALLOC_OR_FAIL(c, cc, 2);
+    HIP_TRY(c, hipMemsetAsync(visited.p, 0, vw * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(cc.p, 0, 8, c->stream));
+    HIP_TRY(c, hipMemsetAsync(counters.p + 1, 0, 20, c->stream));       // the walk's own counters: capped, k-mers seen, next end
+    c->t_begin("unitig_chain_scan", n);
+    chain_scan_kernel<<<std::min<uint32_t>(cdiv(s.n_ends, 256), 2048), 256, 0, c->stream>>>(
+        link, rank, n, LA.p, s.n_ends, k, s.flag_by_rank.p, s.len_by_rank.p, s.start_by_rank.p, s.seed_by_rank.p,
+        counters.p + 4, (unsigned long long*)(counters.p + 2), counters.p + 1, nullptr, flags.p, nullptr, s.cap, visited.p);
+    unvisited_cycle_seeds_kernel<<<cdiv(n, 256), 256, 0, c->stream>>>(link, rank, n, visited.p, outer_link, nrec, cc.p, cc.p + 1);
+    c->t_end();
+    LAUNCH_CHECK(c, "unvisited_cycle_seeds");
+    uint32_t h[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(h, cc.p, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (!h[1]) *new_cuts = h[0];
+    if (c->opt("DBG_DEBUG")) fprintf(stderr, "[unitig] segment route: %llu k-mers on cycles without a cut, %u cycles cut at their seeds%s\n", (unsigned long long)(n - s.seen), h[0], h[1] ? " (a walk gave up)" : "");
+    return 0;
+}
+
+// ---- segment route: long chains are cut into pieces, the pieces are compressed, the pieces are joined ----
+// (also when the chain route met a chain beyond its cap among short ones: a few very long chains in an ordinary graph)
+// n_ends: terminal states of the call's links.  Leaves g empty when the table route has to take the call.
+int Unitigs::segment_route(uint64_t n_ends, GraphDev* g, bool* bad) {
+    // (links: with node records the pieces' walks check every link they take, as the chain route does, and the cutter checks the
+    //  links it removes; without records check_links_kernel has run before)
+    const uint32_t every = c->opt("DBG_SEGMENTS") ? (uint32_t)std::max(2, atoi(c->opt("DBG_SEGMENTS"))) : 128u;   // 32 / 64 / 128 / 256: 112 / 102 / 98 / 103 ms at config-3 size
+    DBuf<uint32_t> link_cut, cyc_list, cyc_ctl;
+    constexpr uint32_t CYC_CAP = 1u << 16;
+    ALLOC_OR_FAIL(c, cyc_list, CYC_CAP); ALLOC_OR_FAIL(c, cyc_ctl, 2);
+    const CycleSeeds cycles{cyc_list.p, cyc_ctl.p, CYC_CAP};
+    uint64_t ends_now = n_ends;                                    // (two more per cycle cut open below)
+    // A cycle cannot be joined the way an open chain is (its cut belongs at its seed k-mer, not at a sampled one): the second
+    // level reports the seed pieces of the cycles it met, their seed k-mers are cut for good, and the route runs once more.
+    for (int attempt = 0; attempt < 3; attempt++) {
+        ALLOC_OR_FAIL(c, link_cut, n2);
+        c->t_begin("unitig_segments", n);
+        HIP_TRY(c, hipMemcpyAsync(link_cut.p, link, (size_t)n2 * 4, hipMemcpyDeviceToDevice, c->stream));
+        cut_links_kernel<<<cdiv(cdiv(n, every), 256), 256, 0, c->stream>>>(link, link_cut.p, nrec, n, every, flags.p);   // (the records are this call's own)
+        c->t_end();
+        LAUNCH_CHECK(c, "cut_links");
+        GraphDev pieces, joined;
+        uint32_t new_cuts = 0;
+        UnitigCall cut = *this;
+        cut.link = link_cut.p;
+        DBG_TRY(Unitigs(c, cut).chain_route(link, &pieces, &new_cuts));
+        link_cut.release();
+        DBG_TRY(links_bad(bad));                                   // a cut link that was not mutual
+        if (*bad) return 0;
+        if (!pieces.filled) {                                        // cycles without a cut among the pieces (or links the walks rejected)
+            if (new_cuts && attempt < 2) { ends_now += 2ull * new_cuts; continue; }   // cut at their seeds: once more
+            if (c->opt("DBG_DEBUG")) fprintf(stderr, "[unitig] segment route: the pieces hold a cycle that could not be cut -> table route\n");
+            break;
+        }
+        const uint64_t n_pieces = pieces.n_nodes;
+        HIP_TRY(c, hipMemsetAsync(cyc_ctl.p, 0, 8, c->stream));
+        const std::string err_before = c->err;
+        const int r = graph_dev_join_segments(c, k, stranded, spec, &pieces, &joined, &cycles);
+        if (r && r != 48) return r;
+        if (r) c->err = err_before;                                // 48: node links not mutual -- the table route decides what that means
+        const bool joined_ok = r == 0 && joined.filled && joined.n_nodes * 2 == ends_now;
+        uint32_t ctl[2] = {0, 0};
+        HIP_TRY(c, hipMemcpyAsync(ctl, cyc_ctl.p, 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (c->opt("DBG_DEBUG")) fprintf(stderr, "[unitig] segment route: %llu pieces (every %u) -> %llu unitigs, %llu chain ends, %u cycles of pieces%s\n",
+                                         (unsigned long long)n_pieces, every, (unsigned long long)joined.n_nodes, (unsigned long long)ends_now, ctl[0],
+                                         joined_ok ? "" : (r == 0 && ctl[0] && ctl[0] <= CYC_CAP && pieces.seed.p && attempt < 2 ? " -> cycles cut at their seeds, once more" : " -> table route"));
+        if (joined_ok) {
+            *g = std::move(joined);
+            c->t_begin("unitig_segments_joined", g->n_nodes);     // (a marker in the timing list: the route ran to its end)
+            c->t_end();
             return 0;
         }
-        // ---- segment route: long chains are cut into pieces, the pieces are compressed, the pieces are joined ----
-        // (also when the chain route met a chain beyond its cap among short ones: a few very long chains in an ordinary graph)
-        if (!ok && (long_chains || res[1] != 0) && !(c->opt("DBG_SEGMENTS") && atoi(c->opt("DBG_SEGMENTS")) == 0)) {
-            // (links: with node records the pieces' walks check every link they take, as the chain route does, and the cutter checks the
-            //  links it removes; without records check_links_kernel has run above)
-            const uint32_t every = c->opt("DBG_SEGMENTS") ? (uint32_t)std::max(2, atoi(c->opt("DBG_SEGMENTS"))) : 128u;   // 32 / 64 / 128 / 256: 112 / 102 / 98 / 103 ms at config-3 size
-            // this level's chain-route buffers go back to the pool: the first level below asks for the same sizes
-            flag_by_rank.release(); len_by_rank.release(); uidx_by_rank.release(); start_by_rank.release(); seed_by_rank.release(); done_bits.release();
-            DBuf<uint32_t> link_cut, cyc_list, cyc_ctl;
-            constexpr uint32_t CYC_CAP = 1u << 16;
-            ALLOC_OR_FAIL(c, cyc_list, CYC_CAP); ALLOC_OR_FAIL(c, cyc_ctl, 2);
-            GraphDev* outer_sink = c->graph_sink;
-            uint64_t ends_now = n_ends;                            // terminal states of the call's links (two more per cycle cut open below)
-            // A cycle cannot be joined the way an open chain is (its cut belongs at its seed k-mer, not at a sampled one): the second
-            // level reports the seed pieces of the cycles it met, their seed k-mers are cut for good, and the route runs once more.
-            for (int attempt = 0; attempt < 3 && !emitted; attempt++) {
-                ALLOC_OR_FAIL(c, link_cut, n2);
-                c->t_begin("unitig_segments", n);
-                HIP_TRY(c, hipMemcpyAsync(link_cut.p, link_dev, (size_t)n2 * 4, hipMemcpyDeviceToDevice, c->stream));
-                cut_links_kernel<<<cdiv(cdiv(n, every), 256), 256, 0, c->stream>>>(link_dev, link_cut.p, const_cast<NodeRec*>(nrec), n, every, flags.p);   // (the records are this call's own)
-                c->t_end();
-                LAUNCH_CHECK(c, "cut_links");
-                GraphDev pieces, joined;
-                c->graph_sink = &pieces;
-                c->segment_outer_links = link_dev;
-                c->segment_new_cuts = 0;
-                c->segment_depth++;
-                dbg_graph sizes_only;
-                bool pieces_done = false;
-                int r = compress_links_device(c, k, n, key_hi, key_lo, exts, data, link_cut.p, rank_dev, spec, stranded, &sizes_only, &pieces_done, nullptr, nrec);
-                c->segment_depth--;
-                c->graph_sink = outer_sink;
-                c->segment_outer_links = nullptr;
-                if (r) return r;
-                link_cut.release();
-                {
-                    bool bad = false;                              // a cut link that was not mutual
-                    DBG_TRY(links_bad(&bad));
-                    if (bad) return 0;
-                }
-                if (!pieces_done) {                                // cycles without a cut among the pieces (or links the walks rejected)
-                    if (c->segment_new_cuts && attempt < 2) { ends_now += 2ull * c->segment_new_cuts; continue; }   // cut at their seeds below: once more
-                    if (c->opt("DBG_DEBUG")) fprintf(stderr, "[unitig] segment route: the pieces hold a cycle that could not be cut -> table route\n");
-                    break;
-                }
-                const uint64_t n_pieces = pieces.n_nodes;
-                HIP_TRY(c, hipMemsetAsync(cyc_ctl.p, 0, 8, c->stream));
-                c->graph_sink = nullptr;                           // (graph_dev_compress installs its own)
-                c->cycle_seed_list = cyc_list.p; c->cycle_seed_count = cyc_ctl.p; c->cycle_seed_cap = CYC_CAP;
-                r = graph_dev_join_segments(c, k, stranded, spec, &pieces, &joined);
-                c->cycle_seed_list = nullptr; c->cycle_seed_count = nullptr; c->cycle_seed_cap = 0;
-                c->graph_sink = outer_sink;
-                if (r && r != 48) return r;                        // 48: node links not mutual -- the table route decides what that means
-                const bool joined_ok = r == 0 && joined.filled && joined.n_nodes * 2 == ends_now;
-                uint32_t ctl[2] = {0, 0};
-                HIP_TRY(c, hipMemcpyAsync(ctl, cyc_ctl.p, 8, hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(c, hipStreamSynchronize(c->stream));
-                if (c->opt("DBG_DEBUG")) fprintf(stderr, "[unitig] segment route: %llu pieces (every %u) -> %llu unitigs, %llu chain ends, %u cycles of pieces%s\n",
-                                                 (unsigned long long)n_pieces, every, (unsigned long long)joined.n_nodes, (unsigned long long)ends_now, ctl[0],
-                                                 joined_ok ? "" : (r == 0 && ctl[0] && ctl[0] <= CYC_CAP && pieces.seed.p && attempt < 2 ? " -> cycles cut at their seeds, once more" : " -> table route"));
-                if (joined_ok) {
-                    words = std::move(joined.words); ustart = std::move(joined.start); ulen = std::move(joined.length);
-                    o_exts = std::move(joined.exts); o_data = std::move(joined.data);
-                    n_nodes = (uint32_t)joined.n_nodes; n_words = joined.n_words; total_bases = joined.n_bases;
-                    emitted = true;
-                    c->t_begin("unitig_segments_joined", n_nodes); // (a marker in the timing list: the route ran to its end)
-                    c->t_end();
-                    break;
-                }
-                if (r || !ctl[0] || ctl[0] > CYC_CAP || !pieces.seed.p) break;
-                cut_at_piece_seeds_kernel<<<cdiv(ctl[0], 256), 256, 0, c->stream>>>(cyc_list.p, ctl[0], pieces.seed.p, link_dev, const_cast<NodeRec*>(nrec), n, cyc_ctl.p + 1);
-                LAUNCH_CHECK(c, "cut_at_piece_seeds");
-                HIP_TRY(c, hipMemcpyAsync(ctl, cyc_ctl.p, 8, hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(c, hipStreamSynchronize(c->stream));
-                if (!ctl[1]) break;
-                ends_now += 2ull * ctl[1];
-            }
-        }
-        if (ok) {
-            DBG_TRY(scan_exclusive_u32(c, flag_by_rank.p, uidx_by_rank.p, n));
-            HIP_TRY(c, hipMemcpyAsync(&n_nodes, uidx_by_rank.p + n, 4, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            const uint32_t nn = std::max<uint32_t>(n_nodes, 1);
-            ALLOC_OR_FAIL(c, ulen, nn); ALLOC_OR_FAIL(c, ufirst, nn); ALLOC_OR_FAIL(c, useed, nn);
-            ALLOC_OR_FAIL(c, ustart, (size_t)n_nodes + 1);
-            ALLOC_OR_FAIL(c, uexts, nn); ALLOC_OR_FAIL(c, uacc, nn); ALLOC_OR_FAIL(c, o_exts, nn); ALLOC_OR_FAIL(c, o_data, nn);
-            gather_chains_kernel<<<cdiv(n, 256), 256, 0, c->stream>>>(flag_by_rank.p, uidx_by_rank.p, len_by_rank.p, start_by_rank.p, seed_by_rank.p, n,
-                                                                      ulen.p, ufirst.p, useed.p);
-            LAUNCH_CHECK(c, "gather_chains");
-            DBG_TRY(scan_exclusive_u32_u64(c, ulen.p, ustart.p, n_nodes));
-            HIP_TRY(c, hipMemcpyAsync(&total_bases, ustart.p + n_nodes, 8, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            n_words = (total_bases + 31) / 32;
-            ALLOC_OR_FAIL(c, words, n_words + 3);
-            HIP_TRY(c, hipMemsetAsync(words.p, 0, (n_words + 3) * 8, c->stream));
-            HIP_TRY(c, hipMemsetAsync(counters.p + 6, 0, 4, c->stream));
-            // The nodes are emitted in two halves so that results can leave while kernels still run: offsets and lengths are
-            // final already, the first half of the sequence words is final when the second half starts.  (A copy into pageable
-            // host memory blocks the host thread, not the device: it is issued on a second stream after the kernels it overlaps.)
-            if (!c->graph_sink) {
-                // (pinned blocks from the ctx's result pool: a copy into pageable memory runs at a third of the link's rate and
-                //  takes a page fault per 4 KB of a fresh array -- 680 MB of graph at config-3 size cost ~40 ms that way)
-                out_early.seq_words = (uint64_t*)ctx_halloc(c, std::max<uint64_t>(n_words, 1) * 8);
-                out_early.start = (uint64_t*)ctx_halloc(c, (size_t)nn * 8);
-                out_early.length = (uint32_t*)ctx_halloc(c, (size_t)nn * 4);
-            }
-            hipStream_t cs = c->graph_sink ? nullptr : c->get_copy_stream();
-            c->t_begin("unitig_emit", n);
-            if (n_nodes) {
-                const uint32_t half = n_nodes / 2;
-                uint64_t first_half_bases = 0;
-                if (half) HIP_TRY(c, hipMemcpyAsync(&first_half_bases, ustart.p + half, 8, hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(c, hipMemsetAsync(counters.p + 6, 0, 8, c->stream));
-                HIP_TRY(c, hipStreamSynchronize(c->stream));
-                hipEvent_t ev = c->get_event();
-                if (half) {
-                    chain_emit_kernel<<<std::min<uint32_t>(cdiv(half, 256), 2048), 256, 0, c->stream>>>(
-                        link_dev, n, k, key_hi, key_lo, exts, data, spec, 0, half, ufirst.p, useed.p, ustart.p, words.p, uexts.p, uacc.p, counters.p + 6, nrec);
-                    LAUNCH_CHECK(c, "chain_emit");
-                }
-                HIP_TRY(c, hipEventRecord(ev, c->stream));
-                chain_emit_kernel<<<std::min<uint32_t>(cdiv(n_nodes - half, 256), 2048), 256, 0, c->stream>>>(
-                    link_dev, n, k, key_hi, key_lo, exts, data, spec, half, n_nodes - half, ufirst.p, useed.p, ustart.p, words.p, uexts.p, uacc.p, counters.p + 7, nrec);
-                LAUNCH_CHECK(c, "chain_emit");
-                finish_nodes_kernel<<<cdiv(n_nodes, 256), 256, 0, c->stream>>>(n_nodes, spec, k, ulen.p, uexts.p, uacc.p, nullptr, o_exts.p, o_data.p);
-                LAUNCH_CHECK(c, "finish_nodes");
-                if (cs) {
-                    HIP_TRY(c, hipMemcpyAsync(out_early.start, ustart.p, (size_t)n_nodes * 8, hipMemcpyDeviceToHost, cs));
-                    HIP_TRY(c, hipMemcpyAsync(out_early.length, ulen.p, (size_t)n_nodes * 4, hipMemcpyDeviceToHost, cs));
-                    early_nodes = true;
-                    // words wholly inside the first half: the word that holds the boundary base may still receive bits
-                    early_words = first_half_bases / 32;
-                    if (early_words) {
-                        HIP_TRY(c, hipStreamWaitEvent(cs, ev, 0));
-                        HIP_TRY(c, hipMemcpyAsync(out_early.seq_words, words.p, early_words * 8, hipMemcpyDeviceToHost, cs));
-                    }
-                    HIP_TRY(c, hipStreamSynchronize(cs));
-                }
-                c->event_pool.push_back(ev);
-            }
-            c->t_end();
-            emitted = true;
-        }
+        if (r || !ctl[0] || ctl[0] > CYC_CAP || !pieces.seed.p) break;
+        cut_at_piece_seeds_kernel<<<cdiv(ctl[0], 256), 256, 0, c->stream>>>(cyc_list.p, ctl[0], pieces.seed.p, link, nrec, n, cyc_ctl.p + 1);
+        LAUNCH_CHECK(c, "cut_at_piece_seeds");
+        HIP_TRY(c, hipMemcpyAsync(ctl, cyc_ctl.p, 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (!ctl[1]) break;
+        ends_now += 2ull * ctl[1];
     }
+    // (to the table route: the cycles cut so far stay cut in `link`, as they are in nrec, which also still carries the sampled cuts of
+    //  the last attempt -- nothing reads nrec after this point)
+    return 0;
+}
 
-    if (!emitted) {
+// ---- table route: every state's walk to its chain end by end walks and doubling, then seeds -> node order -> offsets -> emit ----
+int Unitigs::table_route(const CycleSeeds* seeds, GraphDev* g, bool* bad) {
     if (!links_checked) {                                          // links off the walked chains (cycles, long chains) are unchecked so far
-        DBG_TRY(check_links());
-        bool bad = false;
-        DBG_TRY(links_bad(&bad));
-        if (bad) return 0;
+        DBG_TRY(check_links(bad));
+        if (*bad) return 0;
     }
     DBuf<Jump> JA, JB;
     DBuf<uint32_t> LB;
@@ -1040,7 +1047,7 @@ int compress_links_device(dbg_ctx* c, int k, uint32_t n, const uint64_t* key_hi,
         HIP_TRY(c, hipMemsetAsync(JA.p, 0xFF, (size_t)n2 * sizeof(Jump), c->stream));      // every state UNWRITTEN
         c->t_end();
         c->t_begin("unitig_walk_ends", n);
-        collect_ends_kernel<<<cdiv(n2, 1024 * ENDS_ITEMS), 1024, 0, c->stream>>>(link_dev, avail, n, LA.p, counters.p);
+        collect_ends_kernel<<<cdiv(n2, 1024 * ENDS_ITEMS), 1024, 0, c->stream>>>(link, avail, n, LA.p, counters.p);
         LAUNCH_CHECK(c, "collect_ends");
         uint32_t n_ends = 0;
         HIP_TRY(c, hipMemcpyAsync(&n_ends, counters.p, 4, hipMemcpyDeviceToHost, c->stream));
@@ -1055,7 +1062,7 @@ int compress_links_device(dbg_ctx* c, int k, uint32_t n, const uint64_t* key_hi,
             // 2^14 left 16 % of the states to the doubling (156 ms), 2^15 leaves 3 % (30 ms) for 10 ms more of walking, 2^16 nothing for 36 more
             uint32_t walk_cap = 2 * WALK_CAP;
             if (const char* e = c->opt("DBG_WALK_CAP")) walk_cap = (uint32_t)std::max(16, atoi(e));       // measurement / tests
-            walk_ends_kernel<<<wblocks, 256, 0, c->stream>>>(link_dev, rank_dev, weight, avail, n, LA.p, n_ends, JA.p, counters.p + 4,
+            walk_ends_kernel<<<wblocks, 256, 0, c->stream>>>(link, rank, weight, avail, n, LA.p, n_ends, JA.p, counters.p + 4,
                                                              (unsigned long long*)(counters.p + 2), counters.p + 1, walk_cap);
             LAUNCH_CHECK(c, "walk_ends");
         }
@@ -1082,7 +1089,7 @@ int compress_links_device(dbg_ctx* c, int k, uint32_t n, const uint64_t* key_hi,
             // the states the walkers did not reach start from their one-step links; everything else is final already, in both buffers
             HIP_TRY(c, hipMemsetAsync(counters.p, 0, 4, c->stream));
             c->t_begin("unitig_table_init", n);
-            init_unwritten_kernel<<<cdiv(n2, 1024), 1024, 0, c->stream>>>(link_dev, rank_dev, weight, avail, n, JA.p, LA.p, counters.p);
+            init_unwritten_kernel<<<cdiv(n2, 1024), 1024, 0, c->stream>>>(link, rank, weight, avail, n, JA.p, LA.p, counters.p);
             LAUNCH_CHECK(c, "init_unwritten");
             HIP_TRY(c, hipMemcpyAsync(JB.p, JA.p, (size_t)n2 * sizeof(Jump), hipMemcpyDeviceToDevice, c->stream));
             c->t_end();
@@ -1091,10 +1098,9 @@ int compress_links_device(dbg_ctx* c, int k, uint32_t n, const uint64_t* key_hi,
             la = LA.p;
             if (c->opt("DBG_DEBUG")) fprintf(stderr, "[unitig] doubling over the %u states the walkers left (%.1f %% of %u)\n", n_live, 100.0 * n_live / n2, n2);
         } else {
-            init_states_kernel<<<cdiv(n2, 256), 256, 0, c->stream>>>(link_dev, rank_dev, weight, avail, n, JA.p);
+            init_states_kernel<<<cdiv(n2, 256), 256, 0, c->stream>>>(link, rank, weight, avail, n, JA.p);
             LAUNCH_CHECK(c, "init_states");
         }
-        bool walking = true;
         int rounds = 0;
         const int max_rounds = 34;                                 // 2^33 steps > any chain (+ the finalising round)
         c->t_begin("unitig_pointer_jump", n);
@@ -1108,7 +1114,6 @@ int compress_links_device(dbg_ctx* c, int k, uint32_t n, const uint64_t* key_hi,
             std::swap(a, b);
             la = lb; lb = (lb == LB.p) ? LA.p : LB.p;
             n_live = cnt[0];
-            walking = cnt[1] != 0;
             rounds++;
             if (c->opt("DBG_DEBUG") && partial) fprintf(stderr, "[unitig]   round %d: %u states live\n", rounds, n_live);
         }
@@ -1116,99 +1121,139 @@ int compress_links_device(dbg_ctx* c, int k, uint32_t n, const uint64_t* key_hi,
         // every state's final value is in the buffer written last; states that finished earlier were copied into both
         cur = a;
         if (!n_live) break;
-        (void)walking;
         if (phase == 1) return c->fail(150, "unitig construction: cycle cutting did not terminate");
         // cycles: cut each at its seed's right side and redo the doubling
-        cut_cycles_kernel<<<cdiv(n, 256), 256, 0, c->stream>>>(cur, rank_dev, link_dev, n, c->cycle_seed_list, c->cycle_seed_count, c->cycle_seed_cap);
+        cut_cycles_kernel<<<cdiv(n, 256), 256, 0, c->stream>>>(cur, rank, link, n, seeds ? seeds->list : nullptr, seeds ? seeds->count : nullptr, seeds ? seeds->cap : 0);
         LAUNCH_CHECK(c, "cut_cycles");
     }
     // ---- seeds -> node order -> offsets ----
+    DBuf<uint32_t> flag_by_rank, len_by_rank, uidx_by_rank, uexts, ucnt;
     DBuf<uint8_t> rev_by_rank;
+    DBuf<unsigned long long> uacc;
+    uint32_t n_nodes = 0;
+    uint64_t total_bases = 0;
     ALLOC_OR_FAIL(c, flag_by_rank, n); ALLOC_OR_FAIL(c, len_by_rank, n); ALLOC_OR_FAIL(c, uidx_by_rank, (size_t)n + 1);
     ALLOC_OR_FAIL(c, rev_by_rank, n);
     c->t_begin("unitig_seeds", n);                                  // seeds, node order, offsets, output buffers cleared
     HIP_TRY(c, hipMemsetAsync(flag_by_rank.p, 0, (size_t)n * 4, c->stream));
-    mark_seeds_kernel<<<cdiv(n, 256), 256, 0, c->stream>>>(cur, rank_dev, weight, avail, n, k, flag_by_rank.p, len_by_rank.p, rev_by_rank.p);
+    mark_seeds_kernel<<<cdiv(n, 256), 256, 0, c->stream>>>(cur, rank, weight, avail, n, k, flag_by_rank.p, len_by_rank.p, rev_by_rank.p);
     LAUNCH_CHECK(c, "mark_seeds");
     DBG_TRY(scan_exclusive_u32(c, flag_by_rank.p, uidx_by_rank.p, n));
     HIP_TRY(c, hipMemcpyAsync(&n_nodes, uidx_by_rank.p + n, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    ALLOC_OR_FAIL(c, ulen, std::max<uint32_t>(n_nodes, 1));
-    ALLOC_OR_FAIL(c, ustart, (size_t)n_nodes + 1);
-    ALLOC_OR_FAIL(c, uexts, std::max<uint32_t>(n_nodes, 1));
-    gather_lens_kernel<<<cdiv(n, 256), 256, 0, c->stream>>>(flag_by_rank.p, uidx_by_rank.p, len_by_rank.p, n, ulen.p);
+    const uint32_t nn = std::max<uint32_t>(n_nodes, 1);
+    ALLOC_OR_FAIL(c, g->length, nn); ALLOC_OR_FAIL(c, g->start, (size_t)n_nodes + 1); ALLOC_OR_FAIL(c, uexts, nn);
+    gather_lens_kernel<<<cdiv(n, 256), 256, 0, c->stream>>>(flag_by_rank.p, uidx_by_rank.p, len_by_rank.p, n, g->length.p);
     LAUNCH_CHECK(c, "gather_lens");
-    DBG_TRY(scan_exclusive_u32_u64(c, ulen.p, ustart.p, n_nodes));
-    HIP_TRY(c, hipMemcpyAsync(&total_bases, ustart.p + n_nodes, 8, hipMemcpyDeviceToHost, c->stream));
+    DBG_TRY(scan_exclusive_u32_u64(c, g->length.p, g->start.p, n_nodes));
+    HIP_TRY(c, hipMemcpyAsync(&total_bases, g->start.p + n_nodes, 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    n_words = (total_bases + 31) / 32;
-    ALLOC_OR_FAIL(c, words, n_words + 3);
-    ALLOC_OR_FAIL(c, uacc, std::max<uint32_t>(n_nodes, 1));
-    ALLOC_OR_FAIL(c, o_exts, std::max<uint32_t>(n_nodes, 1));
-    ALLOC_OR_FAIL(c, o_data, std::max<uint32_t>(n_nodes, 1));
-    HIP_TRY(c, hipMemsetAsync(words.p, 0, (n_words + 3) * 8, c->stream));
-    HIP_TRY(c, hipMemsetAsync(uacc.p, 0, (size_t)std::max<uint32_t>(n_nodes, 1) * 8, c->stream));
-    HIP_TRY(c, hipMemsetAsync(uexts.p, 0, (size_t)std::max<uint32_t>(n_nodes, 1) * 4, c->stream));
-    DBuf<uint32_t> ucnt;
+    const uint64_t n_words = (total_bases + 31) / 32;
+    ALLOC_OR_FAIL(c, g->words, n_words + 3); ALLOC_OR_FAIL(c, uacc, nn); ALLOC_OR_FAIL(c, g->exts, nn); ALLOC_OR_FAIL(c, g->data, nn);
+    HIP_TRY(c, hipMemsetAsync(g->words.p, 0, (n_words + 3) * 8, c->stream));
+    HIP_TRY(c, hipMemsetAsync(uacc.p, 0, (size_t)nn * 8, c->stream));
+    HIP_TRY(c, hipMemsetAsync(uexts.p, 0, (size_t)nn * 4, c->stream));
     c->t_end();
     c->t_begin("unitig_emit", n);
     if (nodes) {
-        ALLOC_OR_FAIL(c, ucnt, std::max<uint32_t>(n_nodes, 1));
-        HIP_TRY(c, hipMemsetAsync(ucnt.p, 0, (size_t)std::max<uint32_t>(n_nodes, 1) * 4, c->stream));
+        ALLOC_OR_FAIL(c, ucnt, nn);
+        HIP_TRY(c, hipMemsetAsync(ucnt.p, 0, (size_t)nn * 4, c->stream));
         emit_nodes_kernel<<<cdiv(n, 256), 256, 0, c->stream>>>(cur, n, k, weight, avail, nodes->words, nodes->start, nodes->length, exts, data, spec,
-                                                               uidx_by_rank.p, rev_by_rank.p, ustart.p, words.p, uexts.p, uacc.p, ucnt.p);
+                                                               uidx_by_rank.p, rev_by_rank.p, g->start.p, g->words.p, uexts.p, uacc.p, ucnt.p);
     } else {
-        emit_kernel<<<cdiv(n, 256), 256, 0, c->stream>>>(cur, rank_dev, n, k, key_hi, key_lo, exts, data, spec, uidx_by_rank.p, rev_by_rank.p,
-                                                         ustart.p, words.p, uexts.p, uacc.p);
+        emit_kernel<<<cdiv(n, 256), 256, 0, c->stream>>>(cur, rank, n, k, key_hi, key_lo, exts, data, spec, uidx_by_rank.p, rev_by_rank.p,
+                                                         g->start.p, g->words.p, uexts.p, uacc.p);
     }
     c->t_end();
     LAUNCH_CHECK(c, "emit");
     if (n_nodes) {
-        finish_nodes_kernel<<<cdiv(n_nodes, 256), 256, 0, c->stream>>>(n_nodes, spec, k, ulen.p, uexts.p, uacc.p, nodes ? ucnt.p : nullptr, o_exts.p, o_data.p);
+        finish_nodes_kernel<<<cdiv(n_nodes, 256), 256, 0, c->stream>>>(n_nodes, spec, k, g->length.p, uexts.p, uacc.p, nodes ? ucnt.p : nullptr, g->exts.p, g->data.p);
         LAUNCH_CHECK(c, "finish_nodes");
     }
     if (c->opt("DBG_DEBUG") && n_nodes) {
         unsigned long long a0 = 0; uint32_t d0 = 0, e0 = 0;
-        (void)hipMemcpy(&a0, uacc.p, 8, hipMemcpyDeviceToHost); (void)hipMemcpy(&d0, o_data.p, 4, hipMemcpyDeviceToHost);
+        (void)hipMemcpy(&a0, uacc.p, 8, hipMemcpyDeviceToHost); (void)hipMemcpy(&d0, g->data.p, 4, hipMemcpyDeviceToHost);
         (void)hipMemcpy(&e0, uexts.p, 4, hipMemcpyDeviceToHost);
         fprintf(stderr, "[unitig] nodes=%u spec=%d uacc[0]=%llx o_data[0]=%x uexts[0]=%x uacc.p=%p o_data.p=%p uexts.p=%p\n", n_nodes, spec, a0, d0, e0,
-                (void*)uacc.p, (void*)o_data.p, (void*)uexts.p);
+                (void*)uacc.p, (void*)g->data.p, (void*)uexts.p);
     }
-    }   // general route
-    memset(out, 0, sizeof(*out));
-    out->stranded = stranded ? 1 : 0;
-    out->n_nodes = n_nodes; out->n_seq_words = n_words; out->seq_len_bases = total_bases;
-    if (GraphDev* sink = c->graph_sink) {
-        // the rank-spanning second stage keeps the graph in HBM: the buffers change hands, nothing is copied (out carries the
-        // sizes only, its arrays stay null)
-        sink->words = std::move(words); sink->start = std::move(ustart); sink->length = std::move(ulen);
-        sink->exts = std::move(o_exts); sink->data = std::move(o_data);
-        if (c->segment_depth > 0) sink->seed = std::move(useed);   // (chain route: the pieces' seed k-mers, for cycles found one level up)
-        sink->n_nodes = n_nodes; sink->n_words = n_words; sink->n_bases = total_bases; sink->stranded = stranded ? 1 : 0;
-        sink->filled = true;
+    g->n_nodes = n_nodes; g->n_words = n_words; g->n_bases = total_bases; g->stranded = stranded ? 1 : 0; g->filled = true;
+    return 0;
+}
+
+// The result to its destination.  dev_out (the rank-spanning second stage keeps the graph in HBM): the buffers change hands,
+// nothing is copied.  Otherwise to the host BaseGraph, after what the chain route's early copies have brought over already.
+int Unitigs::deliver(GraphDev& g, const EarlyCopy& early, dbg_graph* out, GraphDev* dev_out) {
+    if (dev_out) {
+        g.seed.release();                                          // (only the segment route's pieces hand their seeds on)
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        *done = true;
+        *dev_out = std::move(g);
         return 0;
     }
-    // ---- to the host BaseGraph ----
-    out->seq_words = out_early.seq_words ? out_early.seq_words : (uint64_t*)ctx_halloc(c, std::max<uint64_t>(n_words, 1) * 8);
-    out->start = out_early.start ? out_early.start : (uint64_t*)ctx_halloc(c, std::max<uint32_t>(n_nodes, 1) * 8ull);
-    out->length = out_early.length ? out_early.length : (uint32_t*)ctx_halloc(c, std::max<uint32_t>(n_nodes, 1) * 4ull);
+    const uint32_t n_nodes = (uint32_t)g.n_nodes;
+    const uint64_t n_words = g.n_words;
+    memset(out, 0, sizeof(*out));
+    out->stranded = stranded ? 1 : 0;
+    out->n_nodes = n_nodes; out->n_seq_words = n_words; out->seq_len_bases = g.n_bases;
+    const dbg_graph& e = early.host;
+    out->seq_words = e.seq_words ? e.seq_words : (uint64_t*)ctx_halloc(c, std::max<uint64_t>(n_words, 1) * 8);
+    out->start = e.start ? e.start : (uint64_t*)ctx_halloc(c, std::max<uint32_t>(n_nodes, 1) * 8ull);
+    out->length = e.length ? e.length : (uint32_t*)ctx_halloc(c, std::max<uint32_t>(n_nodes, 1) * 4ull);
     out->exts = (uint8_t*)ctx_halloc(c, std::max<uint32_t>(n_nodes, 1));
     out->data = (uint32_t*)ctx_halloc(c, std::max<uint32_t>(n_nodes, 1) * 4ull);
     c->t_begin("graph_to_host", n_nodes);
-    if (n_words > early_words)
-        HIP_TRY(c, hipMemcpyAsync(out->seq_words + early_words, words.p + early_words, (n_words - early_words) * 8, hipMemcpyDeviceToHost, c->stream));
+    if (n_words > early.words)
+        HIP_TRY(c, hipMemcpyAsync(out->seq_words + early.words, g.words.p + early.words, (n_words - early.words) * 8, hipMemcpyDeviceToHost, c->stream));
     if (n_nodes) {
-        if (!early_nodes) {
-            HIP_TRY(c, hipMemcpyAsync(out->start, ustart.p, (size_t)n_nodes * 8, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(c, hipMemcpyAsync(out->length, ulen.p, (size_t)n_nodes * 4, hipMemcpyDeviceToHost, c->stream));
+        if (!early.nodes) {
+            HIP_TRY(c, hipMemcpyAsync(out->start, g.start.p, (size_t)n_nodes * 8, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(out->length, g.length.p, (size_t)n_nodes * 4, hipMemcpyDeviceToHost, c->stream));
         }
-        HIP_TRY(c, hipMemcpyAsync(out->exts, o_exts.p, (size_t)n_nodes, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(out->data, o_data.p, (size_t)n_nodes * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(out->exts, g.exts.p, (size_t)n_nodes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(out->data, g.data.p, (size_t)n_nodes * 4, hipMemcpyDeviceToHost, c->stream));
     }
     c->t_end();
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+}  // namespace
+
+// Builds the BaseGraph on the device from the neighbour links u.link (modified when cycles are cut), into exactly one of out (host)
+// and dev_out (HBM).  *done = false (nothing produced) when the links are not mutual or contain a panic marker: the caller then runs
+// the literal host walk.  seeds (second level of the segment route): every cycle cut at its seed is reported there.
+int compress_links_device(dbg_ctx* c, const UnitigCall& u, dbg_graph* out, GraphDev* dev_out, bool* done, const CycleSeeds* seeds) {
+    *done = false;
+    if (u.n == 0 || u.n >= (1u << 30)) return 0;
+    Unitigs b(c, u);
+    const bool try_chains = !u.nodes && !c->opt("DBG_UNITIG_NO_CHAINS") && !c->opt("DBG_UNITIG_NO_WALK");
+    bool bad = false;
+    DBG_TRY(b.open(try_chains && u.nrec, &bad));
+    if (bad) return 0;
+    if (seeds) {
+        self_loop_seeds_kernel<<<cdiv(u.n, 256), 256, 0, c->stream>>>(u.link, u.n, seeds->list, seeds->count, seeds->cap);
+        LAUNCH_CHECK(c, "self_loop_seeds");
+    }
+    GraphDev g;                                                    // filled by the route that takes the call
+    EarlyCopy early;
+    if (try_chains) {
+        Chains s;
+        DBG_TRY(b.chain_scan(c->opt("DBG_SEGMENTS_FORCE") != nullptr, s, &bad));
+        if (bad) return 0;
+        if (s.ok) {
+            DBG_TRY(b.chain_emit(s, &g, out ? &early : nullptr));
+        } else if ((s.long_chains || s.gave_up) && !(c->opt("DBG_SEGMENTS") && atoi(c->opt("DBG_SEGMENTS")) == 0)) {
+            const uint32_t n_ends = s.n_ends;
+            s = Chains();                                          // (back to the pool: the pieces ask for the same sizes)
+            DBG_TRY(b.segment_route(n_ends, &g, &bad));
+            if (bad) return 0;
+        }
+    }
+    if (!g.filled) {
+        DBG_TRY(b.table_route(seeds, &g, &bad));
+        if (bad) return 0;
+    }
+    DBG_TRY(b.deliver(g, early, out, dev_out));
     *done = true;
     return 0;
 }

@@ -124,7 +124,7 @@ def test_sharded_compress_more_shapes_one_gpu(world, reduce, segments):
     """dbg_shard_compress_dev with 3 ranks (an odd tree: one rank sits a level out) and the tree merge: gather is compared node for
     node with the oracle's combine + compress_graph, the tree in canonical form (same unitigs, other order / strand).
     segments: every rank's per-shard unitig construction takes the segment route (unitig.hip: forced, every 3rd k-mer cut) with the
-    shard graph staying in HBM (dbg_ctx::graph_sink set by the caller)."""
+    shard graph staying in HBM (compress_table_dev with a GraphDev destination)."""
     env = dict(os.environ, DBG_SEGMENTS_FORCE="1", DBG_SEGMENTS="3") if segments else None
     r = subprocess.run(["python", "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
                         "--master-port", str(29741 + world + (10 if segments else 0)), os.path.join(ROOT, "tools", "check_sharded_compress.py"), "--backend", "gloo",
