@@ -18,7 +18,8 @@
  *   D1  : none | u8 | u16 | u32.  dbg_filter_kmers[_dev] take every u32 value: a call whose largest label is 2^24 or more runs on
  *         an order-preserving dictionary of its distinct labels (at most 2^24 - 1 of them; round 6); the rank-spanning
  *         dbg_shard_filter_kmers_dev builds that dictionary job-wide (every rank then passes u32 labels).
- *   S   : CountFilter (src/filter.rs:40-63) | CountFilterSet (:68-101).
+ *   S   : CountFilter (src/filter.rs:40-63) | CountFilterSet (:68-101) on the device; any other KmerSummarizer runs on the
+ *         caller's side over the grouped observations that dbg_mi355x_groups.h exports (ABI 7).
  *   spec: SimpleCompress with saturating_add / (a+b)%65535 / max / wrapping add,
  *         or ScmapCompress (src/compression.rs:40-98).
  *
@@ -572,8 +573,8 @@ int  dbg_ctx_probe_slab(dbg_ctx* ctx, uint64_t n_writes, float* ms_out, uint64_t
  * host result blocks (0 = none) into the ctx pools.  A later call of matching size then starts like a warm one. */
 int  dbg_ctx_warm(dbg_ctx* ctx, uint64_t slab_bytes, uint64_t pinned_bytes);
 /* ABI revision of this header: structs only grow at their end from one revision to the next, and a host may check
- * dbg_abi_version() >= the revision it was compiled against before it passes the newer fields (round 6 = 6). */
-#define DBG_ABI_VERSION 6
+ * dbg_abi_version() >= the revision it was compiled against before it passes the newer fields (round 6 = 6; 7 adds the grouped-observation export, dbg_kmer_groups_*). */
+#define DBG_ABI_VERSION 7
 uint32_t dbg_abi_version(void);
 
 #ifdef __cplusplus

@@ -2,6 +2,7 @@
 // over the C ABI in dbg_mi355x.h.  The crate is Rust (no toolchain in the build image), so this header
 // plays the part of the Rust shim: same names, argument meaning and error behaviour
 //     filter_kmers<K>(seqs, summarizer, stranded, report_all_kmers, memory_size)     src/filter.rs:139-148
+//         (CountFilter / CountFilterSet on the device; any other summarizer S on the host over the grouped observations)
 //     msp_sequence<P>(k, seq, permutation, rc)                                        src/msp.rs:279-288
 //     compress_kmers_with_hash<K>(stranded, spec, index)                              src/compression.rs:588-594
 //     compress_graph<K>(stranded, spec, graph, censor_nodes), BaseGraph::combine      src/compression.rs:338-349, graph.rs:71-100
@@ -18,6 +19,7 @@
 #include <utility>
 #include <vector>
 #include "dbg_mi355x.h"
+#include "dbg_mi355x_groups.h"
 
 namespace debruijn {
 
@@ -198,6 +200,49 @@ std::pair<KmerIndex<K, std::vector<uint8_t>>, std::vector<K>> filter_kmers(Conte
     }
     for (uint64_t i = 0; i < t.n_all; i++) all.push_back(K::from_hi_lo(t.all_hi[i], t.all_lo[i]));
     dbg_free_table(ctx.raw(), &t);
+    return {std::move(idx), std::move(all)};
+}
+
+// filter_kmers::<K, DnaString, u8, DS, S> for any other KmerSummarizer (filter.rs:27-35): the device groups the observations
+// (dbg_mi355x_groups.h), S runs on the host.  S::summarize(obs) receives one k-mer's observations as a
+// std::vector<std::tuple<K, Exts, uint8_t>> in input order and returns std::tuple<bool, Exts, DS> (valid, accumulated Exts,
+// summary).  The CountFilter / CountFilterSet overloads above stay the better match for those two.
+template <class K, class S>
+auto filter_kmers(Context& ctx, const std::vector<std::tuple<DnaString, Exts, uint8_t>>& seqs, const S& summarizer, bool stranded,
+                  bool report_all_kmers, size_t memory_size)
+    -> std::pair<KmerIndex<K, std::tuple_element_t<2, decltype(summarizer.summarize(std::declval<const std::vector<std::tuple<K, Exts, uint8_t>>&>()))>>,
+                 std::vector<K>> {
+    using Obs = std::vector<std::tuple<K, Exts, uint8_t>>;
+    using DS = std::tuple_element_t<2, decltype(summarizer.summarize(std::declval<const Obs&>()))>;
+    if (memory_size == 0) throw Panic("attempt to divide by zero: memory_size = 0 (filter.rs:158)");
+    detail::Flat<DnaString> f(seqs);
+    dbg_seqset dev{};
+    ctx.check(dbg_seqset_to_device(ctx.raw(), &f.ss, &dev));
+    struct DevGuard { dbg_ctx* c; dbg_seqset* d; ~DevGuard() { dbg_seqset_free_device(c, d); } } guard{ctx.raw(), &dev};
+    uint32_t bounds[257], n_passes = 0;
+    ctx.check(dbg_kmer_groups_plan_dev(ctx.raw(), &dev, (uint32_t)K::k(), stranded, 0, bounds, &n_passes));
+    KmerIndex<K, DS> idx;
+    std::vector<K> all;
+    Obs obs;
+    for (uint32_t pi = 0; pi < n_passes; pi++) {
+        dbg_group_params gp{(uint32_t)K::k(), stranded, bounds[pi], bounds[pi + 1], 0, 0};
+        dbg_kmer_groups gd{}, g{};
+        ctx.check(dbg_kmer_groups_dev(ctx.raw(), &dev, &gp, &gd));
+        const int rc = dbg_groups_to_host(ctx.raw(), &gd, &g);
+        dbg_free_groups(ctx.raw(), &gd);
+        ctx.check(rc);
+        try {
+            for (uint64_t i = 0; i < g.n; i++) {
+                const K kmer = K::from_hi_lo(g.key_hi[i], g.key_lo[i]);
+                obs.clear();
+                for (uint64_t j = g.obs_off[i]; j < g.obs_off[i + 1]; j++) obs.emplace_back(kmer, Exts(g.obs_exts[j]), (uint8_t)g.obs_data[j]);
+                auto r = summarizer.summarize((const Obs&)obs);
+                if (report_all_kmers) all.push_back(kmer);
+                if (std::get<0>(r)) { idx.keys.push_back(kmer); idx.exts.push_back(std::get<1>(r)); idx.data.push_back(std::move(std::get<2>(r))); }
+            }
+        } catch (...) { dbg_free_groups(ctx.raw(), &g); throw; }
+        dbg_free_groups(ctx.raw(), &g);
+    }
     return {std::move(idx), std::move(all)};
 }
 

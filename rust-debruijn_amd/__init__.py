@@ -19,7 +19,8 @@ from . import _capi
 from ._capi import SeqSet as _SeqSet
 
 __all__ = ["Context", "Exts", "CountFilter", "CountFilterSet", "SimpleCompress", "ScmapCompress",
-           "PackedDnaStringSet", "KmerTable", "BaseGraph", "filter_kmers", "msp_sequence",
+           "PackedDnaStringSet", "KmerTable", "BaseGraph", "filter_kmers", "KmerGroups", "SummaryTable", "kmer_groups",
+           "kmer_group_passes", "iter_kmer_groups", "msp_sequence",
            "compress_kmers_with_hash", "compress_graph", "combine_graphs", "remove_censored_exts", "remove_censored_exts_sharded",
            "synth_reads_host", "pack_bases", "unpack_bases", "DbgError", "LEFT", "RIGHT"]
 
@@ -405,7 +406,21 @@ def filter_kmers(seqs, summarizer, stranded, report_all_kmers, memory_size, k, c
     seqs: HostSeqs or an iterable of (bases, Exts, d).  Returns (KmerTable, all_kmers) where
     all_kmers is the list of every observed k-mer (ascending) iff report_all_kmers, else [].
     compact_sets: ask the library for the narrow CSR of a CountFilterSet table (dbg_filter_params.compact_sets); the mirror
-    widens it again, so the result is the same table."""
+    widens it again, so the result is the same table.
+
+    summarizer: CountFilter / CountFilterSet (anything with a `kind`) run on the device.  Any other object is a KmerSummarizer
+    (src/filter.rs:27-35) run on the host over the grouped observations the device exports (kmer_groups), through one of
+      summarize(items)          the trait verbatim: items iterates (kmer, Exts, d) of one k-mer in input order -> (valid, Exts, DS)
+      summarize_groups(groups)  vectorised: one pass's KmerGroups -> (valid bool array, exts array, data sequence / array)
+    (summarize_groups is preferred when both exist).  An optional attribute min_obs_export (see kmer_groups) spares the copy of
+    the observations of k-mers the summarizer rejects anyway.  The table is then a SummaryTable whose data(i) is the DS.
+    D1 crosses to the device as itself only when every d is None (unit) or every d is an int / numpy integer in 0..2^32 - 1;
+    any other D1 (floats, strings, tuples, a mix) is never converted: the observations carry their sequence's index, summarize
+    receives the caller's own values, and summarize_groups receives groups whose obs_data holds the sequence indices and whose
+    seq_data is the list of per-sequence values (an observation's D1 is groups.seq_data[groups.obs_data[j]]; groups.observations(i)
+    does the lookup)."""
+    if not hasattr(summarizer, "kind"):
+        return _filter_kmers_generic(seqs, summarizer, stranded, report_all_kmers, memory_size, k, ctx)
     ctx = ctx or default_context()
     hs = seqs if isinstance(seqs, HostSeqs) else HostSeqs.from_tuples(seqs)
     p = _capi.FilterParams(k, int(bool(stranded)), summarizer.kind, summarizer.min_kmer_obs,
@@ -418,6 +433,223 @@ def filter_kmers(seqs, summarizer, stranded, report_all_kmers, memory_size, k, c
     finally:
         ctx.lib.dbg_free_table(ctx.h, C.byref(t))
     all_kmers = [(int(h) << 64) | int(l) for h, l in zip(out.all_hi, out.all_lo)]
+    return out, all_kmers
+
+
+# ------------------------------------------------------------------------------------------------
+# grouped k-mer observations: filter_kmers with any KmerSummarizer (include/dbg_mi355x_groups.h)
+# ------------------------------------------------------------------------------------------------
+class KmerGroups:
+    """What filter_kmers hands to KmerSummarizer::summarize (src/filter.rs:186-221), as arrays: the distinct canonical k-mers
+    in ascending order (key_hi / key_lo), per k-mer its observation count (nobs) and the OR of their Exts (exts_or), and its
+    observations obs_off[i] .. obs_off[i + 1] in input order (obs_exts, obs_data: D1 widened to u32, or the source sequence's
+    index with obs_seq_index; None for unit D1).  Groups below min_obs_export have an empty observation segment."""
+
+    def __init__(self, k):
+        self.k = k
+        self.key_hi = self.key_lo = np.zeros(0, np.uint64)
+        self.nobs = np.zeros(0, np.uint32)
+        self.exts_or = np.zeros(0, np.uint8)
+        self.obs_off = np.zeros(1, np.uint64)
+        self.obs_exts = np.zeros(0, np.uint8)
+        self.obs_data = None
+        self.n_kmer_instances = 0
+        self.bounds = [0, 256]
+        self.seq_data = None        # per-sequence D1 values when obs_data holds sequence indices (filter_kmers, non-integer D1)
+
+    def __len__(self):
+        return len(self.key_lo)
+
+    def keys(self):
+        return [(int(h) << 64) | int(l) for h, l in zip(self.key_hi, self.key_lo)]
+
+    def kmer(self, i):
+        return (int(self.key_hi[i]) << 64) | int(self.key_lo[i])
+
+    def observations(self, i, data=None):
+        """[(Exts, d)] of group i in input order; data: per-sequence values to look obs_data up in (obs_seq_index; default
+        seq_data)"""
+        a, b = int(self.obs_off[i]), int(self.obs_off[i + 1])
+        data = self.seq_data if data is None else data
+        if self.obs_data is None:
+            ds = [None] * (b - a)
+        elif data is None:
+            ds = [int(x) for x in self.obs_data[a:b]]
+        else:
+            ds = [data[int(x)] for x in self.obs_data[a:b]]
+        return [(Exts(e), d) for e, d in zip(self.obs_exts[a:b], ds)]
+
+    @staticmethod
+    def concat(parts, k):
+        out = KmerGroups(k)
+        if not parts:
+            return out
+        cat = lambda name: np.concatenate([getattr(q, name) for q in parts])
+        out.key_hi, out.key_lo, out.nobs, out.exts_or, out.obs_exts = (cat(n) for n in ("key_hi", "key_lo", "nobs", "exts_or", "obs_exts"))
+        out.obs_data = None if parts[0].obs_data is None else cat("obs_data")
+        offs, base = [np.zeros(1, np.uint64)], 0
+        for q in parts:
+            offs.append(q.obs_off[1:] + np.uint64(base))
+            base += int(q.obs_off[-1])
+        out.obs_off = np.concatenate(offs)
+        out.n_kmer_instances = sum(q.n_kmer_instances for q in parts)
+        out.bounds = [parts[0].bounds[0]] + [q.bounds[-1] for q in parts]
+        return out
+
+
+class _DevSeqs:
+    """a HostSeqs uploaded once (dbg_seqset_to_device) for every pass of an export"""
+
+    def __init__(self, ctx, hs):
+        self.ctx, self.hs = ctx, hs
+        self.host = hs.c_struct()
+        self.dev = _SeqSet()
+        ctx.check(ctx.lib.dbg_seqset_to_device(ctx.h, C.byref(self.host), C.byref(self.dev)))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.ctx.lib.dbg_seqset_free_device(self.ctx.h, C.byref(self.dev))
+
+
+def _group_passes(ctx, dev, k, stranded, max_obs_per_pass):
+    bounds = (C.c_uint32 * 257)()
+    n = C.c_uint32()
+    ctx.check(ctx.lib.dbg_kmer_groups_plan_dev(ctx.h, C.byref(dev), k, int(bool(stranded)), int(max_obs_per_pass), bounds, C.byref(n)))
+    return [int(bounds[i]) for i in range(n.value + 1)]
+
+
+def _groups_pass(ctx, dev, k, stranded, lo, hi, min_obs_export, obs_seq_index):
+    gp = _capi.GroupParams(k, int(bool(stranded)), lo, hi, int(min_obs_export), int(bool(obs_seq_index)))
+    gd, gh = _capi.KmerGroups(), _capi.KmerGroups()
+    ctx.check(ctx.lib.dbg_kmer_groups_dev(ctx.h, C.byref(dev), C.byref(gp), C.byref(gd)))
+    try:
+        ctx.check(ctx.lib.dbg_groups_to_host(ctx.h, C.byref(gd), C.byref(gh)))
+    finally:
+        ctx.lib.dbg_free_groups(ctx.h, C.byref(gd))
+    try:
+        out = KmerGroups(k)
+        n = gh.n
+        out.key_hi, out.key_lo = _copy(gh.key_hi, n, np.uint64), _copy(gh.key_lo, n, np.uint64)
+        out.nobs, out.exts_or = _copy(gh.nobs, n, np.uint32), _copy(gh.exts_or, n, np.uint8)
+        out.obs_off = _copy(gh.obs_off, n + 1, np.uint64) if n else np.zeros(1, np.uint64)
+        out.obs_exts = _copy(gh.obs_exts, gh.n_obs, np.uint8)
+        out.obs_data = _copy(gh.obs_data, gh.n_obs, np.uint32) if gh.obs_data else None
+        out.n_kmer_instances = gh.n_kmer_instances
+        out.bounds = [lo, hi]
+    finally:
+        ctx.lib.dbg_free_groups(ctx.h, C.byref(gh))
+    return out
+
+
+def _as_host_seqs(seqs):
+    return seqs if isinstance(seqs, HostSeqs) else HostSeqs.from_tuples(seqs)
+
+
+def kmer_group_passes(seqs, k, stranded, max_obs_per_pass=0, ctx=None):
+    """dbg_kmer_groups_plan_dev: the ascending bucket bounds [0, .., 256] of the export's passes (each at most max_obs_per_pass
+    k-mer instances; 0 = what the device's memory allows)"""
+    ctx = ctx or default_context()
+    with _DevSeqs(ctx, _as_host_seqs(seqs)) as d:
+        return _group_passes(ctx, d.dev, k, stranded, max_obs_per_pass)
+
+
+def iter_kmer_groups(seqs, k, stranded, min_obs_export=0, obs_seq_index=False, max_obs_per_pass=0, bounds=None, ctx=None):
+    """KmerGroups of each pass in ascending bucket order (the reads are uploaded once); bounds: as kmer_group_passes returns"""
+    ctx = ctx or default_context()
+    with _DevSeqs(ctx, _as_host_seqs(seqs)) as d:
+        bounds = bounds or _group_passes(ctx, d.dev, k, stranded, max_obs_per_pass)
+        for lo, hi in zip(bounds[:-1], bounds[1:]):
+            yield _groups_pass(ctx, d.dev, k, stranded, lo, hi, min_obs_export, obs_seq_index)
+
+
+def kmer_groups(seqs, k, stranded, min_obs_export=0, obs_seq_index=False, max_obs_per_pass=0, bounds=None, ctx=None):
+    """Every k-mer's observations as one KmerGroups (the passes concatenated).  min_obs_export > 0: groups of fewer observations
+    keep key, nobs and exts_or but no observations (right for summarizers that reject them anyway).  obs_seq_index: obs_data
+    holds each observation's sequence index instead of its D1."""
+    parts = list(iter_kmer_groups(seqs, k, stranded, min_obs_export, obs_seq_index, max_obs_per_pass, bounds, ctx))
+    return KmerGroups.concat(parts, k)
+
+
+class SummaryTable(KmerTable):
+    """filter_kmers' table for a host-side summarizer: ds[i] is the DS the summarizer returned for k-mer i (a numpy array when
+    every DS is an integer -- then `compress_kmers_with_hash(..., data=table.ds)` takes it as is -- a list otherwise)."""
+
+    def __init__(self, k):
+        super().__init__(k)
+        self.ds = []
+
+    def data(self, i):
+        d = self.ds[i]
+        return int(d) if isinstance(d, np.integer) else d
+
+
+def _is_u32_label(d):
+    """an integer D1 that passes to the device unchanged (bool and int subclasses such as enums keep their type on the host path)"""
+    return (type(d) is int or isinstance(d, np.integer)) and 0 <= int(d) < 1 << 32
+
+
+def _summarize_pass(summarizer, g, data_lookup):
+    if hasattr(summarizer, "summarize_groups"):
+        valid, exts, data = summarizer.summarize_groups(g)
+        valid = np.asarray(valid, bool)
+        return valid, np.asarray(exts, np.uint8), data
+    valid, exts, data = np.zeros(len(g), bool), np.zeros(len(g), np.uint8), []
+    for i in range(len(g)):
+        kmer = g.kmer(i)
+        items = ((kmer, e, d) for e, d in g.observations(i, data_lookup))
+        v, e, ds = summarizer.summarize(items)
+        valid[i], exts[i] = bool(v), int(e)
+        data.append(ds)
+    return valid, exts, data
+
+
+def _filter_kmers_generic(seqs, summarizer, stranded, report_all_kmers, memory_size, k, ctx):
+    if int(memory_size) == 0:
+        raise DbgError("attempt to divide by zero: memory_size = 0 (filter.rs:158)")
+    data_lookup, obs_seq_index = None, False
+    if isinstance(seqs, HostSeqs):
+        hs = seqs
+    else:
+        seqs = list(seqs)
+        ds = [s[2] for s in seqs]
+        if all(d is None for d in ds) or all(_is_u32_label(d) for d in ds):
+            hs = HostSeqs.from_tuples(seqs)
+        else:
+            # D1 that is no u8/u16/u32 (the trait allows any Clone): never converted -- the observations carry their sequence's
+            # index and the value is looked up on the host
+            hs = HostSeqs.from_tuples([(s[0], s[1], None) for s in seqs])
+            data_lookup, obs_seq_index = ds, True
+    ctx = ctx or default_context()
+    min_export = int(getattr(summarizer, "min_obs_export", 0) or 0)
+    keys_hi, keys_lo, exts_l, data_l, all_hi, all_lo = [], [], [], [], [], []
+    n_inst, n_passes = 0, 0
+    for g in iter_kmer_groups(hs, k, stranded, min_export, obs_seq_index, ctx=ctx):
+        g.seq_data = data_lookup
+        valid, exts, data = _summarize_pass(summarizer, g, data_lookup)
+        if len(valid) != len(g) or len(exts) != len(g) or len(data) != len(g):
+            raise ValueError("the summarizer must return one valid flag, Exts and DS per k-mer group")
+        keys_hi.append(g.key_hi[valid]); keys_lo.append(g.key_lo[valid]); exts_l.append(exts[valid])
+        if isinstance(data, np.ndarray):
+            data_l.append(data[valid])
+        else:
+            data_l.append([d for d, v in zip(data, valid) if v])
+        if report_all_kmers:
+            all_hi.append(g.key_hi); all_lo.append(g.key_lo)
+        n_inst += g.n_kmer_instances
+        n_passes += 1
+    out = SummaryTable(k)
+    cat = lambda xs, dt: np.concatenate(xs).astype(dt) if xs else np.zeros(0, dt)
+    out.key_hi, out.key_lo, out.exts = cat(keys_hi, np.uint64), cat(keys_lo, np.uint64), cat(exts_l, np.uint8)
+    flat = [d for part in data_l for d in part]
+    if all(isinstance(d, (int, np.integer)) and not isinstance(d, bool) for d in flat) and all(0 <= int(d) < 1 << 32 for d in flat):
+        out.ds = np.array([int(d) for d in flat], np.uint32) if flat else np.zeros(0, np.uint32)
+    else:
+        out.ds = flat
+    out.n_kmer_instances = n_inst
+    out.n_passes = n_passes
+    all_kmers = [(int(h) << 64) | int(l) for h, l in zip(cat(all_hi, np.uint64), cat(all_lo, np.uint64))] if report_all_kmers else []
     return out, all_kmers
 
 

@@ -24,6 +24,7 @@ def _sources():
 def _headers():
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
     hs.append(os.path.join(os.path.dirname(HERE), "include", "dbg_mi355x.h"))
+    hs.append(os.path.join(os.path.dirname(HERE), "include", "dbg_mi355x_groups.h"))
     return hs
 
 

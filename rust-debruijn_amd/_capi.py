@@ -29,6 +29,17 @@ class KmerTable(C.Structure):
                 ("set_off_width", C.c_uint32), ("set_val_width", C.c_uint32)]
 
 
+class GroupParams(C.Structure):
+    _fields_ = [("k", C.c_uint32), ("stranded", C.c_int32), ("bucket_lo", C.c_uint32), ("bucket_hi", C.c_uint32),
+                ("min_obs_export", C.c_uint64), ("obs_seq_index", C.c_int32)]
+
+
+class KmerGroups(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("key_hi", C.c_void_p), ("key_lo", C.c_void_p), ("nobs", C.c_void_p), ("exts_or", C.c_void_p),
+                ("obs_off", C.c_void_p), ("obs_exts", C.c_void_p), ("obs_data", C.c_void_p), ("n_obs", C.c_uint64),
+                ("n_kmer_instances", C.c_uint64), ("bucket_lo", C.c_uint32), ("bucket_hi", C.c_uint32), ("on_device", C.c_int32)]
+
+
 class MspParams(C.Structure):
     _fields_ = [("k", C.c_uint32), ("p", C.c_uint32), ("permutation", C.c_void_p), ("rc", C.c_int32),
                 ("lmer_words", C.c_uint32)]
@@ -127,6 +138,9 @@ EXPORTS = [
     "dbg_pack_acgt", "dbg_pack_acgt_dev", "dbg_pack_acgt_hashn", "dbg_pack_acgt_hashn_dev", "dbg_unpack_acgt", "dbg_unpack_acgt_dev",
 ]
 
+# every symbol include/dbg_mi355x_groups.h (the grouped-observation export, ABI 7) declares
+GROUP_EXPORTS = ["dbg_kmer_groups_plan_dev", "dbg_kmer_groups_dev", "dbg_groups_to_host", "dbg_free_groups"]
+
 _lib = None
 
 
@@ -165,6 +179,12 @@ def load():
     lib.dbg_free_table.argtypes = [C.c_void_p, C.POINTER(KmerTable)]
     lib.dbg_free_table.restype = None
     lib.dbg_table_to_host.argtypes = [C.c_void_p, C.POINTER(KmerTable), C.POINTER(KmerTable)]
+    lib.dbg_kmer_groups_plan_dev.argtypes = [C.c_void_p, C.POINTER(SeqSet), C.c_uint32, C.c_int, C.c_uint64, C.c_void_p,
+                                             C.POINTER(C.c_uint32)]
+    lib.dbg_kmer_groups_dev.argtypes = [C.c_void_p, C.POINTER(SeqSet), C.POINTER(GroupParams), C.POINTER(KmerGroups)]
+    lib.dbg_groups_to_host.argtypes = [C.c_void_p, C.POINTER(KmerGroups), C.POINTER(KmerGroups)]
+    lib.dbg_free_groups.argtypes = [C.c_void_p, C.POINTER(KmerGroups)]
+    lib.dbg_free_groups.restype = None
     lib.dbg_remove_censored_exts.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(KmerTable), C.c_int]
     lib.dbg_msp_sequence.argtypes = [C.c_void_p, C.POINTER(SeqSet), C.POINTER(MspParams), C.POINTER(MspPieces)]
     lib.dbg_msp_sequence_dev.argtypes = lib.dbg_msp_sequence.argtypes

@@ -67,6 +67,10 @@ int kmer_top_byte_hist(dbg_ctx* ctx, const SeqDev& s, int k, bool stranded, unsi
 int kmer_counts_range(dbg_ctx* ctx, const SeqDev& s, int k, bool stranded, uint32_t b_lo, uint32_t b_hi, uint32_t* kcount);
 int extract_kmers_range(dbg_ctx* ctx, const SeqDev& s, const uint64_t* koff, uint64_t n_kmers, int k, bool stranded, uint32_t b_lo, uint32_t b_hi,
                         RecArrays out);
+// the grouped-observation export (groups.hip): records of [b_lo, b_hi) with payload = the record's index in the pass, the
+// observation's Exts in inst_exts and its D1 -- or, seq_index, its sequence's index -- in inst_val (may be null)
+int extract_kmers_obs(dbg_ctx* ctx, const SeqDev& s, const uint64_t* koff, uint64_t n_kmers, int k, bool stranded, uint32_t b_lo, uint32_t b_hi,
+                      bool seq_index, RecArrays out, uint8_t* inst_exts, uint32_t* inst_val);
 
 // ---- radix.hip : stable LSD radix sort of records by (key, selected payload bits) -----------
 // Sorts n (< 2^32) records.  key_bits = 2k significant key bits; pay_shift/pay_bits select payload

@@ -148,7 +148,63 @@ __global__ void __launch_bounds__(256) extract_range_kernel(SeqDev s, const uint
         }
     }
 }
+// The grouped-observation export's form of extract_range_kernel: the payload is the record's own index within the pass (the
+// sort carries it along; stability keeps a group's observations in input order), and the observation itself goes to
+// per-instance arrays: its Exts byte, and its full-width D1 (or, with seq_index, the index of its sequence).  inst_val may be null.
+template <bool STRANDED, bool HAS_HI>
+__global__ void __launch_bounds__(256) extract_obs_kernel(SeqDev s, const uint64_t* __restrict__ koff, int k, uint32_t b_lo, uint32_t b_hi,
+                                                          bool seq_index, uint64_t* __restrict__ out_hi, uint64_t* __restrict__ out_lo,
+                                                          uint32_t* __restrict__ out_pay, uint8_t* __restrict__ inst_exts,
+                                                          uint32_t* __restrict__ inst_val) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t lt = lanemask_lt();
+    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    for (uint64_t si = wave; si < s.n; si += n_waves) {
+        const uint32_t len = s.length[si];
+        if (len < (uint32_t)k) continue;
+        const uint64_t st = s.start[si];
+        const uint32_t nk = len - (uint32_t)k + 1;
+        const uint32_t sexts = s.exts ? s.exts[si] : 0u;
+        const uint32_t val = seq_index ? (uint32_t)si : load_d1(s.data, s.data_width, si);
+        uint64_t o = koff[si];
+        for (uint32_t j0 = 0; j0 < nk; j0 += 64) {
+            const uint32_t j = j0 + lane;
+            bool in = false, flipped = false;
+            K128 km{0, 0};
+            if (j < nk) { km = canon_kmer<STRANDED>(s.words, s.n_words ? s.n_words - 1 : 0, st + j, k, &flipped); const uint32_t b = key_top_byte(km, k); in = b >= b_lo && b < b_hi; }
+            const uint64_t m = __ballot(in);
+            if (in) {
+                uint32_t left = j == 0 ? (sexts & 0x0fu) : (1u << packed_get(s.words, st + j - 1));
+                uint32_t right = (j + (uint32_t)k == len) ? (sexts & 0xf0u) : (16u << packed_get(s.words, st + j + k));
+                uint32_t ex = left | right;
+                if (flipped) ex = exts_rc(ex);
+                const uint64_t q = o + (uint32_t)__popcll(m & lt);
+                if (HAS_HI) out_hi[q] = km.hi;
+                out_lo[q] = km.lo;
+                out_pay[q] = (uint32_t)q;
+                inst_exts[q] = (uint8_t)ex;
+                if (inst_val) inst_val[q] = val;
+            }
+            o += (uint32_t)__popcll(m);
+        }
+    }
+}
 }  // namespace
+
+int extract_kmers_obs(dbg_ctx* ctx, const SeqDev& s, const uint64_t* koff, uint64_t n_kmers, int k, bool stranded, uint32_t b_lo, uint32_t b_hi,
+                      bool seq_index, RecArrays out, uint8_t* inst_exts, uint32_t* inst_val) {
+    if (s.n == 0 || n_kmers == 0) return 0;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((s.n + 3) / 4, 256ull * 16);
+    ctx->t_begin("groups_extract", n_kmers);
+    const bool has_hi = out.hi != nullptr;
+#define GO(ST, HH) extract_obs_kernel<ST, HH><<<blocks, 256, 0, ctx->stream>>>(s, koff, k, b_lo, b_hi, seq_index, out.hi, out.lo, out.pay, inst_exts, inst_val)
+    if (stranded) { if (has_hi) GO(true, true); else GO(true, false); }
+    else          { if (has_hi) GO(false, true); else GO(false, false); }
+#undef GO
+    ctx->t_end();
+    LAUNCH_CHECK(ctx, "extract_kmers_obs");
+    return 0;
+}
 
 int kmer_top_byte_hist(dbg_ctx* ctx, const SeqDev& s, int k, bool stranded, unsigned long long* hist_dev /* [256], zeroed here */) {
     HIP_TRY(ctx, hipMemsetAsync(hist_dev, 0, 256 * 8, ctx->stream));

@@ -8,6 +8,7 @@ every struct has the header's fields in the header's order, and the C layout com
 field under the C ABI's natural alignment) equals ctypes.sizeof / field offsets of the mirror structure.
 
     python tools/gen_rust_ffi.py            # rewrites integration/dbg_mi355x_sys.rs
+    python tools/gen_rust_ffi.py --groups   # rewrites integration/dbg_mi355x_groups_sys.rs from include/dbg_mi355x_groups.h
 """
 import os
 import re
@@ -16,6 +17,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "dbg_mi355x.h")
 OUT = os.path.join(ROOT, "integration", "dbg_mi355x_sys.rs")
+GROUPS_HEADER = os.path.join(ROOT, "include", "dbg_mi355x_groups.h")
+GROUPS_OUT = os.path.join(ROOT, "integration", "dbg_mi355x_groups_sys.rs")
 
 PRIM = {"uint64_t": "u64", "uint32_t": "u32", "uint16_t": "u16", "uint8_t": "u8", "int32_t": "i32", "int64_t": "i64", "int": "c_int",
         "double": "f64", "float": "f32", "char": "c_char", "void": "c_void", "size_t": "usize"}
@@ -128,6 +131,22 @@ def emit(structs, enums, funcs):
     return "\n".join(o)
 
 
+def emit_groups(structs, enums, funcs):
+    """the companion header's binding: its own structs and functions over the types of the main binding (a sibling module)"""
+    body = emit(structs, enums, funcs).split("\n")
+    start = body.index("#[repr(C)] pub struct dbg_ctx { _private: [u8; 0] }      // opaque")
+    o = ["//! Raw FFI of the grouped-observation export (`include/dbg_mi355x_groups.h`, ABI 7): generated by `tools/gen_rust_ffi.py --groups`,",
+         "//! do not edit.  A sibling of `dbg_mi355x_sys.rs` (dbg_ctx, dbg_seqset); INTEGRATION.md section 3b sketches the generic shim.",
+         "#![allow(non_camel_case_types, non_snake_case, dead_code)]",
+         "use std::os::raw::c_int;",
+         "use super::dbg_mi355x_sys::{dbg_ctx, dbg_seqset};",
+         ""]
+    rest = body[start + 1:]
+    while rest and not rest[0]:
+        rest = rest[1:]
+    return "\n".join(o + rest)
+
+
 def c_layout(fields):
     """(size, [(name, offset)]) of a #[repr(C)] struct from its Rust field types (natural alignment, LP64)"""
     off, align_max, out = 0, 1, []
@@ -145,6 +164,11 @@ def c_layout(fields):
 
 
 def main():
+    if "--groups" in sys.argv[1:]:
+        structs, enums, funcs = parse(open(GROUPS_HEADER).read())
+        open(GROUPS_OUT, "w").write(emit_groups(structs, enums, funcs))
+        print("%s: %d structs, %d functions" % (os.path.relpath(GROUPS_OUT, ROOT), len(structs), len(funcs)))
+        return
     structs, enums, funcs = parse(open(HEADER).read())
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
     open(OUT, "w").write(emit(structs, enums, funcs))
